@@ -6,6 +6,12 @@ python bench.py --gpus N --steps K --warmup W
          16-row bands of the SAME 1080p frame (the frame's band partition) and the frame
          is composed on rank 0 over RCCL/xGMI send/recv (rrte_hip_render_gather_async) -> strong scaling.
 A "step" is one frame.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up (W frames in flight, then 2 x min(K, 20) frames one after another, by which
+the measured tile order is in effect), times the K steps and prints the headline (value, ms_per_step, config).
+  --dump-outputs DIR  also writes the frame the last timed step rendered, as DIR/frame_rgba8.npy
+  --full              also measures everything beside the headline (per-launch roofline, verification against
+                      the oracle, latency, boundary, kernel kinds, stock config, BASELINE configs, CPU baselines)
 """
 from __future__ import annotations
 
@@ -54,6 +60,13 @@ def parse():
     ap.add_argument("--spp", type=int, default=None, help="override samples per pixel (profiling other configs)")
     ap.add_argument("--max-depth", type=int, default=None, help="override max_depth")
     ap.add_argument("--random", action="store_true", help="random jitter (and scatter) instead of pixel centres")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the per-launch passes and rooflines, the verification against the "
+                         "oracle, frame latency and D2H, the drop-in boundary, the kernel kinds, the stock config, "
+                         "the other BASELINE configs and the CPU baselines (the --no-* options trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the last timed step rendered to DIR/frame_rgba8.npy (float32, H x W x 4; "
+                         "a fixed seeded sample of its pixels when the frame is over 64 MB)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the CPU baseline sample")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-stock", action="store_true", help="skip the stock-config secondary measurement")
@@ -190,6 +203,22 @@ def verify_frames(frames_u8, timed_shadow, steps, ref, refs=None, shadow_total=N
             "shadow_rays_match": int(timed_shadow) == int(shadow_total),
             "shadow_rays_per_frame": {"timed_mean": timed_shadow / steps, "oracle": shadow_total / steps},
             "reference": "oracle/rrte_oracle.c (C restatement of Raytracer::render), same scene and parameters"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, frame_u8, W, H):
+    """--dump-outputs: the RGBA8 frame a caller of the timed path receives, as float32.  Up to the size
+    limit the whole frame (H, W, 4) in frame_rgba8.npy; a larger frame as a fixed sample of 2^21 of its
+    pixels (seeded: the same pixels from run to run, in image order) in frame_rgba8_sample.npy."""
+    px = frame_u8.reshape(H * W, 4).astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    if px.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(Path(dirname) / "frame_rgba8.npy", px.reshape(H, W, 4))
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(H * W, size=1 << 21, replace=False))
+        np.save(Path(dirname) / "frame_rgba8_sample.npy", px[idx])
 
 
 def flop_tally(scene, params):
@@ -453,6 +482,7 @@ def config_leg(name, W, H, mode, dev, cpu_budget_s, flight=4, target_s=0.5):
 
 def main():
     args = parse()
+    full = args.full
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -526,7 +556,7 @@ def main():
     streams = [torch.cuda.Stream(dev) for _ in range(max(F, args.streams) if gath else F)]
     NS = max(1, min(args.streams, len(streams))) if gath else F  # caller streams the gather frames rotate over
     fulls = [torch.empty(W * H, dtype=torch.int32, device=dev) for _ in range(F)]
-    full, stream = fulls[0], streams[0]
+    stream = streams[0]
     torch.cuda.set_stream(stream)
     sptrs = [C.c_void_p(s.cuda_stream) for s in streams]
     assert all(p.value for p in sptrs), "need non-null HIP stream handles"
@@ -553,27 +583,35 @@ def main():
         step(i)
     torch.cuda.synchronize(dev)
 
-    # per-launch kernel duration (roofline): frames strictly one after another on one stream
-    # (N > 1: each frame rendered and gathered on its own)
+    # 2 x n_seq more warm-up frames strictly one after another on one stream (N > 1: each frame rendered and
+    # gathered on its own): the measured tile order is profiled on the first frames and takes effect a few
+    # frames later, so after the in-flight warm-up alone a short run's timed steps would still render in image
+    # order.  --full times these frames: the per-launch kernel duration (roofline)
+    n_seq = min(args.steps, 20)
     if gath:
         ctx.check(lib.rrte_hip_set_gather_batch(ctx.h, 1))
-    n_seq = min(args.steps, 20)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_seq)]
-    for i in range(n_seq):
-        evs[i][0].record(stream)
-        step(0)
-        evs[i][1].record(stream)
-    torch.cuda.synchronize(dev)
-    launch_ms = [a.elapsed_time(b) for a, b in evs]
-    # the same frames back to back between two events: an event pair around every launch also times the
-    # stream's gap before and after it (~20 us), so the per-launch figure is the pair's span / frames
-    b2b = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-    b2b[0].record(stream)
-    for i in range(n_seq):
-        step(0)
-    b2b[1].record(stream)
-    torch.cuda.synchronize(dev)
-    b2b_ms = b2b[0].elapsed_time(b2b[1]) / n_seq
+    if not full:
+        for _ in range(2):
+            for i in range(n_seq):
+                step(0)
+            torch.cuda.synchronize(dev)
+    else:
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_seq)]
+        for i in range(n_seq):
+            evs[i][0].record(stream)
+            step(0)
+            evs[i][1].record(stream)
+        torch.cuda.synchronize(dev)
+        launch_ms = [a.elapsed_time(b) for a, b in evs]
+        # the same frames back to back between two events: an event pair around every launch also times the
+        # stream's gap before and after it (~20 us), so the per-launch figure is the pair's span / frames
+        b2b = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        b2b[0].record(stream)
+        for i in range(n_seq):
+            step(0)
+        b2b[1].record(stream)
+        torch.cuda.synchronize(dev)
+        b2b_ms = b2b[0].elapsed_time(b2b[1]) / n_seq
     ctx.check(lib.rrte_hip_synchronize(ctx.h))  # folds warm-up and sequential-pass shadow counts away
 
     if gath:
@@ -609,7 +647,10 @@ def main():
     st = ctx.stats()
     elapsed = t1 - t0
     # the timed frames themselves, for the verification against the oracle (outside the timed region)
-    timed_frames = [f.cpu().numpy().view(np.uint8).copy() for f in fulls[:min(F, args.steps)]] if rank == 0 else []
+    timed_frames = ([f.cpu().numpy().view(np.uint8).copy() for f in fulls[:min(F, args.steps)]]
+                    if rank == 0 and full else [])
+    if rank == 0 and args.dump_outputs:  # the last timed step's frame, before anything else renders into its buffer
+        dump_outputs(args.dump_outputs, fulls[(args.steps - 1) % F].cpu().numpy().view(np.uint8), W, H)
     rows = H
     if dist_on:  # this rank's rows under the frame's band partition (sky bands on the root, the rest round robin)
         sky, rb, pb = C.c_uint32(), C.c_uint32(), C.c_uint32()
@@ -631,34 +672,35 @@ def main():
         dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
         primary, shadow, jit_ranks = int(cnt[0].item()), int(cnt[1].item()), int(cnt[2].item())
 
-    # single-frame latency (enqueue -> frame complete on the device), D2H of the frame separately;
+    # --full: single-frame latency (enqueue -> frame complete on the device), D2H of the frame separately;
     # N > 1: each frame gathered on its own
-    if gath:
-        ctx.check(lib.rrte_hip_set_gather_batch(ctx.h, 1))
-    lat = []
-    for _ in range(5):
-        if dist_on:
-            dist.barrier()
+    if full:
+        if gath:
+            ctx.check(lib.rrte_hip_set_gather_batch(ctx.h, 1))
+        lat = []
+        for _ in range(5):
+            if dist_on:
+                dist.barrier()
+            torch.cuda.synchronize(dev)
+            a = time.perf_counter()
+            step()
+            torch.cuda.synchronize(dev)
+            lat.append(time.perf_counter() - a)
+        latency_ms = statistics.median(lat) * 1e3
+        host = torch.empty(W * H, dtype=torch.int32, pin_memory=True)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        host.copy_(fulls[0], non_blocking=True)
+        e1.record(stream)
         torch.cuda.synchronize(dev)
-        a = time.perf_counter()
-        step()
-        torch.cuda.synchronize(dev)
-        lat.append(time.perf_counter() - a)
-    latency_ms = statistics.median(lat) * 1e3
-    host = torch.empty(W * H, dtype=torch.int32, pin_memory=True)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    host.copy_(full, non_blocking=True)
-    e1.record(stream)
-    torch.cuda.synchronize(dev)
-    d2h_ms = e0.elapsed_time(e1)
+        d2h_ms = e0.elapsed_time(e1)
 
     # The drop-in boundary as Engine::render_frame uses it (engine.rs:280-312 -> raytracer.rs:45-89):
     # blocking rrte_hip_render into a host RGBA8 buffer, D2H included -- into a reused buffer, and
     # into a fresh zeroed buffer per frame as the reference allocates one (`vec![0u8; w*h*4]`,
     # raytracer.rs:54).  Not the headline (SURVEY §8d excludes D2H); rank 0, N = 1 only.
     boundary = None
-    if world == 1 and not args.no_boundary:
+    if full and world == 1 and not args.no_boundary:
         hbuf = np.zeros(W * H * 4, dtype=np.uint8)
         pout = lambda b: b.ctypes.data_as(C.POINTER(C.c_uint8))  # noqa: E731
         for _ in range(3):
@@ -747,7 +789,7 @@ def main():
                                           "frame buffer allocated page-locked (hipHostMalloc), zero copy as well"}
 
     kinds = None
-    if world == 1 and not args.no_stock:
+    if full and world == 1 and not args.no_stock:
         anim = [scenes.animate_values(LoweredScene(objs, lights, cam), f) for f in range(8)]
         kinds = kernel_variants(scene, prm, fulls, sptrs, dev, W * H * prm.samples_per_pixel + shadow // args.steps,
                                 anim=anim)
@@ -755,7 +797,7 @@ def main():
     # the reference's stock config (rank 0, N=1 only; not the headline) on the headline's context: its
     # own scene-specialised REFCOMPAT kernel (runtime sample / bounce loops), compiled on the warm-up frames
     stock = None
-    if world == 1 and not args.no_stock:
+    if full and world == 1 and not args.no_stock:
         sscene, sprm = stock_config(args)
         for i in range(2):
             ctx.check(lib.rrte_hip_render_async(ctx.h, sscene.ref(), C.byref(sprm), fulls[i % F].data_ptr(), None,
@@ -773,7 +815,7 @@ def main():
                  "value": round(W * H * 4 / ts / 1e6, 3), "unit": "Msample/s", "ms_per_frame": round(ts * 1e3, 4)}
 
     legs = None
-    if world == 1 and not args.no_legs:
+    if full and world == 1 and not args.no_legs:
         legs = {}
         for key, name, lw, lh, lmode, desc in LEGS:
             legs[key] = config_leg(name, lw, lh, lmode, dev, cpu_budget_s=args.cpu_seconds)
@@ -782,20 +824,6 @@ def main():
     if rank == 0:
         rays = primary + shadow
         value = rays / elapsed / 1e6
-        # per launch: the back-to-back span / frames (what rocprof's average kernel duration is compared
-        # with); the per-frame event brackets' median and mean are reported beside it
-        mean_launch_ms = float(np.mean(launch_ms))
-        median_launch_ms = float(np.median(launch_ms))
-        avg_launch_ms = b2b_ms
-        # algorithmic HBM bytes per launch: the RGBA8 framebuffer store, 4 B per pixel (SURVEY §8d);
-        # the scene (<= a few KB) is served from the scalar cache and counts once.
-        bytes_per_launch = 4 * W * rows
-        achieved = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9
-        flops_frame, _, _ = flop_tally(scene, prm)
-        flops_launch = flops_frame * rows / H
-        valu_tf = flops_launch / (avg_launch_ms * 1e-3) / 1e12
-        wl = f"{args.scene}@{W}x{H}/{args.mode}"
-        pmc, pmc_note = pmc_traffic(wl, abi.build_id())
         line = {
             "metric": "Mray/s (primary+shadow) at 1920x1080, sdf-showcase scene; 1/2/4/8 GPU",
             "value": round(value, 3),
@@ -822,41 +850,8 @@ def main():
                 "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
                 "parallelism": f"rows{world}" if world > 1 else "single",
             },
-            # the binding roofline: VALU FP32 (no dense contraction, no MFMA).  achieved =
-            # algorithmic FP32 ops of one launch (the oracle's instrumented counting build) / the
-            # average launch duration; HBM beside it (4 B/pixel frame store, PMC traffic)
-            "roofline": {
-                "bound": "valu",
-                "achieved": round(valu_tf, 3),
-                "peak": VALU_PEAK_TFLOPS,
-                "unit": "TFLOP/s",
-                "frac": valu_tf / VALU_PEAK_TFLOPS,
-                "traffic": pmc["hbm_bytes_per_launch"] if pmc else None,
-                "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, profiles/pmc_*.json of this build)",
-                "profile": pmc_note,
-                "flops_per_launch": flops_launch,
-                "frac_of_unpacked_peak": valu_tf / (VALU_PEAK_TFLOPS / 2),
-                "achieved_at_frame_rate": round(flops_launch / (elapsed / args.steps) / 1e12, 3),
-                "kernel": ("rrte_jit_kernel (scene-specialised, hiprtc)" if st.jit_active else
-                           "rrte::ray_kernel<%s> (generic)" % ("LAMBERT_SHADOW" if args.mode == "lambert_shadow" else "REFCOMPAT")),
-                "jit_compile_ms": round(st.jit_compile_ms, 1) if st.jit_active else None,
-                "jit_active_ranks": f"{jit_ranks}/{world}",
-                "avg_launch_ms": round(avg_launch_ms, 5),
-                "bracket_median_ms": round(median_launch_ms, 5),
-                "bracket_mean_ms": round(mean_launch_ms, 5),
-                "avg_launch_note": f"HIP events around {n_seq} frames run back to back on one stream, span / {n_seq}; "
-                                   "launch_ms_each: an event pair around each frame (includes the stream gap)",
-                "launch_ms_each": [round(x, 4) for x in launch_ms],
-                "note": "peak = packed-FP32 vector peak (MI355X_MICROARCH.md); the kernel issues unpacked FP32, one ray "
-                        "per lane" + ("" if world == 1 else f"; N > 1: rank 0's share, flops scaled by its rows ({rows}/{H})"),
-                "hbm": {"achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": achieved / HBM_PEAK_GBS, "bytes_per_launch": bytes_per_launch,
-                        "traffic": pmc["hbm_bytes_per_launch"] if pmc else None,
-                        "note": "algorithmic bytes = the 4 B/pixel RGBA8 frame store"},
-            },
         }
         line["primary_only"] = {"value": round(primary / elapsed / 1e6, 3), "unit": "Mray/s"}
-        line["frame_latency_ms"] = round(latency_ms, 4)
         line["host_enqueue_ms_per_step"] = round((t_enq - t0) / args.steps * 1e3, 4)
         # hot-first tile order: slots of the timed frames' launches dispatched first
         env_order = os.environ.get("RRTE_TILE_ORDER", "")
@@ -864,6 +859,54 @@ def main():
                               "tiles": ((W + 7) // 8) * ((rows + 7) // 8),
                               "mode": {"0": "image order", "2": "fixed permutation (tests)"}.get(
                                   env_order, "measured cost, slowest first (default)")}
+    if rank == 0 and full:
+        # per launch: the back-to-back span / frames (what rocprof's average kernel duration is compared
+        # with); the per-frame event brackets' median and mean are reported beside it
+        mean_launch_ms = float(np.mean(launch_ms))
+        median_launch_ms = float(np.median(launch_ms))
+        avg_launch_ms = b2b_ms
+        # algorithmic HBM bytes per launch: the RGBA8 framebuffer store, 4 B per pixel (SURVEY §8d);
+        # the scene (<= a few KB) is served from the scalar cache and counts once.
+        bytes_per_launch = 4 * W * rows
+        achieved = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9
+        flops_frame, _, _ = flop_tally(scene, prm)
+        flops_launch = flops_frame * rows / H
+        valu_tf = flops_launch / (avg_launch_ms * 1e-3) / 1e12
+        wl = f"{args.scene}@{W}x{H}/{args.mode}"
+        pmc, pmc_note = pmc_traffic(wl, abi.build_id())
+        # the binding roofline: VALU FP32 (no dense contraction, no MFMA).  achieved =
+        # algorithmic FP32 ops of one launch (the oracle's instrumented counting build) / the
+        # average launch duration; HBM beside it (4 B/pixel frame store, PMC traffic)
+        line["roofline"] = {
+            "bound": "valu",
+            "achieved": round(valu_tf, 3),
+            "peak": VALU_PEAK_TFLOPS,
+            "unit": "TFLOP/s",
+            "frac": valu_tf / VALU_PEAK_TFLOPS,
+            "traffic": pmc["hbm_bytes_per_launch"] if pmc else None,
+            "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, profiles/pmc_*.json of this build)",
+            "profile": pmc_note,
+            "flops_per_launch": flops_launch,
+            "frac_of_unpacked_peak": valu_tf / (VALU_PEAK_TFLOPS / 2),
+            "achieved_at_frame_rate": round(flops_launch / (elapsed / args.steps) / 1e12, 3),
+            "kernel": ("rrte_jit_kernel (scene-specialised, hiprtc)" if st.jit_active else
+                       "rrte::ray_kernel<%s> (generic)" % ("LAMBERT_SHADOW" if args.mode == "lambert_shadow" else "REFCOMPAT")),
+            "jit_compile_ms": round(st.jit_compile_ms, 1) if st.jit_active else None,
+            "jit_active_ranks": f"{jit_ranks}/{world}",
+            "avg_launch_ms": round(avg_launch_ms, 5),
+            "bracket_median_ms": round(median_launch_ms, 5),
+            "bracket_mean_ms": round(mean_launch_ms, 5),
+            "avg_launch_note": f"HIP events around {n_seq} frames run back to back on one stream, span / {n_seq}; "
+                               "launch_ms_each: an event pair around each frame (includes the stream gap)",
+            "launch_ms_each": [round(x, 4) for x in launch_ms],
+            "note": "peak = packed-FP32 vector peak (VALU_PEAK_TFLOPS); the kernel issues unpacked FP32, one ray "
+                    "per lane" + ("" if world == 1 else f"; N > 1: rank 0's share, flops scaled by its rows ({rows}/{H})"),
+            "hbm": {"achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "bytes_per_launch": bytes_per_launch,
+                    "traffic": pmc["hbm_bytes_per_launch"] if pmc else None,
+                    "note": "algorithmic bytes = the 4 B/pixel RGBA8 frame store"},
+        }
+        line["frame_latency_ms"] = round(latency_ms, 4)
         line["d2h_ms"] = round(d2h_ms, 4)  # frame to pinned host memory, excluded from `value`
         if pmc and pmc.get("valu") is not None:
             line["valu"] = dict(pmc["valu"])
@@ -912,6 +955,7 @@ def main():
             line["config"]["flyby_poses"] = K
         else:
             line["verified"] = verify_frames(timed_frames, shadow, args.steps, ref)  # (shadow: summed over ranks)
+    if rank == 0:
         print(json.dumps(line), flush=True)
     ctx.close()
     if dist_on:

@@ -6,7 +6,7 @@ OUT=$1; shift
 ARGS=("$@")
 run() {  # label, VAR=value...
   local label=$1; shift
-  r=$(env "$@" timeout -k 10 120 python bench.py --no-cpu --no-stock --steps 60 --warmup 5 "${ARGS[@]}" \
+  r=$(env "$@" timeout -k 10 120 python bench.py --full --no-cpu --no-stock --steps 60 --warmup 5 "${ARGS[@]}" \
       | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["roofline"]["avg_launch_ms"])') || return 1
   echo "$label $r" >> $OUT
 }

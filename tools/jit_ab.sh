@@ -10,7 +10,7 @@ for r in 1 2; do
   k=0
   for o in "$@"; do
     for st in 200 20; do
-      RRTE_JIT_EXTRA_OPTS="$o" timeout -k 10 200 python -u bench.py --no-cpu --no-stock --steps $st > gpurun_out/ab.log 2>&1 || { tail -5 gpurun_out/ab.log; exit 1; }
+      RRTE_JIT_EXTRA_OPTS="$o" timeout -k 10 200 python -u bench.py --full --no-cpu --no-stock --steps $st > ${OUT%/*}/ab.log 2>&1 || { tail -5 ${OUT%/*}/ab.log; exit 1; }
       tail -1 gpurun_out/ab.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print("'"v$k [$o] steps=$st"'", d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["frame_latency_ms"])' | tee -a $OUT
     done
     RRTE_JIT_EXTRA_OPTS="$o" timeout -k 10 200 python -u bench.py --no-cpu --no-stock --scene deformation-stress --width 3840 --height 2160 --steps 10 --warmup 3 > gpurun_out/ab.log 2>&1 || { tail -5 gpurun_out/ab.log; exit 1; }

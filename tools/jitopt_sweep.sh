@@ -8,7 +8,7 @@ OPTS=("" "-mllvm -amdgpu-sched-strategy=max-ilp" "-mllvm -amdgpu-sched-strategy=
       "-mllvm -amdgpu-sched-strategy=max-memory-clause" "-O2")
 for round in 1 2; do
   for o in "${OPTS[@]}"; do
-    r=$(RRTE_JIT_EXTRA_OPTS="$o" timeout -k 10 150 python bench.py --no-cpu --no-stock --steps 40 "$@" |
+    r=$(RRTE_JIT_EXTRA_OPTS="$o" timeout -k 10 150 python bench.py --full --no-cpu --no-stock --steps 40 "$@" |
         python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["roofline"]["jit_compile_ms"])') || exit 1
     echo "round$round [$o] $r" | tee -a "$OUT"
   done

@@ -11,7 +11,7 @@ for round in 1 2; do
     if [ -n "$w" ]; then export RRTE_JIT_MIN_WAVES=$w; else unset RRTE_JIT_MIN_WAVES; fi
     if [ "$st" = default ]; then unset RRTE_JIT_EXTRA_OPTS; else export RRTE_JIT_EXTRA_OPTS="-mllvm -amdgpu-sched-strategy=$st"; fi
     for steps in 20 200; do
-      r=$(timeout -k 10 200 python bench.py --steps $steps --warmup 5 --no-legs --no-stock --no-cpu --no-boundary \
+      r=$(timeout -k 10 200 python bench.py --full --steps $steps --warmup 5 --no-legs --no-stock --no-cpu --no-boundary \
           | python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["verified"]["u8_max_diff"], d["verified"]["shadow_rays_match"])') || exit 1
       echo "r$round [$s] steps=$steps ms_per_step/avg_launch/u8/shadow_ok = $r"
     done

@@ -5,7 +5,7 @@
 set -o pipefail
 for k in 1 2; do
   for w in 8 0 6; do
-    RRTE_JIT_MIN_WAVES=$w timeout -k 10 300 python bench.py --no-cpu --no-boundary --steps 5 --warmup 2 > /tmp/sw.json || exit 1
+    RRTE_JIT_MIN_WAVES=$w timeout -k 10 300 python bench.py --full --no-cpu --no-boundary --steps 5 --warmup 2 > /tmp/sw.json || exit 1
     python3 -c "import json; d=json.loads(open('/tmp/sw.json').read().strip().splitlines()[-1]); s=d['stock_config']; print('r$k min_waves=$w stock', s['ms_per_frame'], 'ms', s['value'], s['unit'])"
   done
 done

@@ -24,7 +24,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
         sys.exit(0)
     import bench
     sys.argv = ["bench.py", "--scene", "deformation-stress", "--width", "3840", "--height", "2160",
-                "--no-cpu", "--no-stock", "--steps", "6", "--warmup", "2"]
+                "--full", "--no-cpu", "--no-stock", "--steps", "6", "--warmup", "2"]
     bench.main()
     sys.exit(0)
 
