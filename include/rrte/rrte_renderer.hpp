@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../rrte_hip.h"
+#include "../rrte_hip_query.h"
 
 namespace rrte_math {
 
@@ -388,6 +389,16 @@ public:
     // parity variant: RGBA8 plus the float image (post-gamma, or linear pre-gamma)
     std::pair<std::vector<uint8_t>, std::vector<float>> render_f32(const Objects& objects, const Lights& lights,
                                                                    const Camera& camera, bool linear = false);
+    // Ray queries (include/rrte_hip_query.h): the closest hit of each ray -- ray_color's search
+    // (raytracer.rs:103-113) over the ray's own [t_min, t_max] -- or, with any_hit, the first object in
+    // list order that occludes it.  `lights`: the lights the scene is rendered with, so that a query
+    // between frames finds the scene cached on the device.
+    std::vector<rrte_ray_hit> raycast(const Objects& objects, const std::vector<rrte_ray>& rays, bool any_hit = false,
+                                      const Lights& lights = {});
+    // The closest hit under each pixel (x, y) of the configured width x height frame seen by `camera`:
+    // the frame's own pixel-centre primary ray, t_min = config.t_min.
+    std::vector<rrte_ray_hit> pick(const Objects& objects, const Camera& camera,
+                                   const std::vector<std::pair<uint32_t, uint32_t>>& pixels, const Lights& lights = {});
     rrte_stats stats() const;
     // the C ABI call on an already lowered scene (diagnostics, tests/cpp/cpp_mirror_tool.cpp)
     void render_raw(const rrte_scene_ir& ir, const rrte_render_params& p, uint8_t* out) {

@@ -9,6 +9,8 @@ import ctypes as C
 import os
 from pathlib import Path
 
+import numpy as np
+
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("RRTE_HIP_LIB", _HERE / "lib" / "librrte_hip.so"))
 
@@ -151,6 +153,36 @@ EXPORTS = {
     "rrte_hip_set_comm_timeout": (C.c_int, [_P, C.c_uint32]),
 }
 
+# ------------------------------------------------ ray queries (include/rrte_hip_query.h)
+QUERY_CLOSEST, QUERY_ANY = 0, 1
+QUERY_MAX_RAYS = 1 << 24
+
+
+class Ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("t_min", C.c_float), ("direction", C.c_float * 3), ("t_max", C.c_float)]
+
+
+class RayHit(C.Structure):
+    _fields_ = [("t", C.c_float), ("prim", C.c_int32), ("point", C.c_float * 3), ("normal", C.c_float * 3),
+                ("front_face", C.c_uint32), ("tri", C.c_uint32), ("material", C.c_int32), ("_pad", C.c_uint32)]
+
+
+assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 48
+
+# The same records as numpy structured dtypes (arrays of them are what Raytracer.raycast / pick pass and return).
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_min", "<f4"), ("direction", "<f4", (3,)), ("t_max", "<f4")])
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4"), ("point", "<f4", (3,)), ("normal", "<f4", (3,)),
+                          ("front_face", "<u4"), ("tri", "<u4"), ("material", "<i4"), ("_pad", "<u4")])
+assert RAY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 48
+
+# Every entry point include/rrte_hip_query.h declares (EXPORTS above stays the set of rrte_hip.h).
+QUERY_EXPORTS = {
+    "rrte_hip_raycast": (C.c_int, [_P, C.POINTER(SceneIR), C.POINTER(Ray), C.c_uint32, C.c_uint32, C.POINTER(RayHit)]),
+    "rrte_hip_raycast_async": (C.c_int, [_P, C.POINTER(SceneIR), _P, C.c_uint32, C.c_uint32, _P, _P]),
+    "rrte_hip_pick": (C.c_int, [_P, C.POINTER(SceneIR), C.POINTER(RenderParams), C.POINTER(C.c_uint32), C.c_uint32,
+                                C.POINTER(RayHit)]),
+}
+
 _lib = None
 
 
@@ -171,7 +203,7 @@ def load() -> C.CDLL:
     except Exception:
         pass
     lib = C.CDLL(str(LIB_PATH), mode=C.RTLD_GLOBAL)
-    for name, (res, args) in EXPORTS.items():
+    for name, (res, args) in {**EXPORTS, **QUERY_EXPORTS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -644,6 +644,29 @@ std::pair<std::vector<uint8_t>, std::vector<float>> Raytracer::render_f32(const 
     check(rrte_hip_render_f32(ctx_, &sc.ir(), &p, out8.data(), outf.data()));
     return {std::move(out8), std::move(outf)};
 }
+std::vector<rrte_ray_hit> Raytracer::raycast(const Objects& objects, const std::vector<rrte_ray>& rays, bool any_hit,
+                                             const Lights& lights) {
+    const LoweredScene sc(objects, lights, Camera{});
+    std::vector<rrte_ray_hit> hits(rays.size());
+    check(rrte_hip_raycast(ctx_, &sc.ir(), rays.data(), (uint32_t)rays.size(),
+                           any_hit ? RRTE_QUERY_ANY : RRTE_QUERY_CLOSEST, hits.data()));
+    return hits;
+}
+std::vector<rrte_ray_hit> Raytracer::pick(const Objects& objects, const Camera& camera,
+                                          const std::vector<std::pair<uint32_t, uint32_t>>& pixels,
+                                          const Lights& lights) {
+    const LoweredScene sc(objects, lights, camera);
+    const rrte_render_params p = config_.lower();
+    std::vector<uint32_t> xy;
+    xy.reserve(2 * pixels.size());
+    for (const auto& px : pixels) {
+        xy.push_back(px.first);
+        xy.push_back(px.second);
+    }
+    std::vector<rrte_ray_hit> hits(pixels.size());
+    check(rrte_hip_pick(ctx_, &sc.ir(), &p, xy.data(), (uint32_t)pixels.size(), hits.data()));
+    return hits;
+}
 rrte_stats Raytracer::stats() const {
     rrte_stats s;
     check(rrte_hip_stats(ctx_, &s));

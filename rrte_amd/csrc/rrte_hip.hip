@@ -33,6 +33,7 @@
 #include "jit.hpp"
 #include "sdf_guard.hpp"
 #include "ray_kernels.hpp"
+#include "ray_query.hpp"
 
 using namespace rrte;
 
@@ -114,6 +115,9 @@ struct rrte_ctx {
     // frame buffers for the blocking entry points
     uint32_t* d_rgba = nullptr; size_t cap_rgba = 0;
     float4* d_f32 = nullptr; size_t cap_f32 = 0;
+    // staging of the blocking ray queries (rrte_hip_raycast / rrte_hip_pick): rays or pixel pairs in, hits out
+    uint8_t* d_qin = nullptr; size_t cap_qin = 0;
+    uint8_t* d_qout = nullptr; size_t cap_qout = 0;
     unsigned long long* d_counters = nullptr;   // shadow rays, kCounterShards x kCounterStride (accumulating)
     unsigned long long* h_counters = nullptr;   // pinned copy
     unsigned long long shadow_base = 0;         // value at the start of the last frame
@@ -586,16 +590,8 @@ bool sdf_program_ok(const rrte_sdf_node* nodes, uint32_t count) {
     return sp == 1 && pp == 0;
 }
 
-rrte_status validate(rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_params* p) {
-    if (!s || !p) return fail(c, RRTE_INVALID_ARG, "null scene or params");
-    if (p->width == 0 || p->height == 0) return fail(c, RRTE_INVALID_ARG, "zero-sized frame %ux%u", p->width, p->height);
-    if ((uint64_t)p->width * p->height > (1ull << 30)) return fail(c, RRTE_INVALID_ARG, "frame too large");
-    if (p->samples_per_pixel == 0) return fail(c, RRTE_INVALID_ARG, "samples_per_pixel must be >= 1");
-    if (p->mode > RRTE_MODE_LAMBERT_SHADOW) return fail(c, RRTE_INVALID_ARG, "unknown mode %u", p->mode);
-    if (p->jitter > RRTE_JITTER_RANDOM) return fail(c, RRTE_INVALID_ARG, "unknown jitter %u", p->jitter);
-    // (the high bits are the library's own per-launch flags, kFlagSlabRgb24 / kFlagHostStore)
-    if (p->flags & ~(uint32_t)(RRTE_FLAG_F32_LINEAR | RRTE_FLAG_GATHER_OVERLAP))
-        return fail(c, RRTE_INVALID_ARG, "unknown flags 0x%x", p->flags);
+// The part of validate() that concerns the scene alone (the ray queries validate only this).
+rrte_status validate_scene(rrte_ctx* c, const rrte_scene_ir* s) {
     if ((s->num_prims && !s->prims) || (s->num_lights && !s->lights) || (s->num_materials && !s->materials) ||
         (s->num_sdf_nodes && !s->sdf_nodes))
         return fail(c, RRTE_INVALID_ARG, "null array with nonzero count");
@@ -625,6 +621,19 @@ rrte_status validate(rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_para
         if (s->materials[i].kind > RRTE_MAT_EMISSIVE)
             return fail(c, RRTE_UNSUPPORTED_PRIM, "material %u: unknown kind %u", i, s->materials[i].kind);
     return RRTE_OK;
+}
+
+rrte_status validate(rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_params* p) {
+    if (!s || !p) return fail(c, RRTE_INVALID_ARG, "null scene or params");
+    if (p->width == 0 || p->height == 0) return fail(c, RRTE_INVALID_ARG, "zero-sized frame %ux%u", p->width, p->height);
+    if ((uint64_t)p->width * p->height > (1ull << 30)) return fail(c, RRTE_INVALID_ARG, "frame too large");
+    if (p->samples_per_pixel == 0) return fail(c, RRTE_INVALID_ARG, "samples_per_pixel must be >= 1");
+    if (p->mode > RRTE_MODE_LAMBERT_SHADOW) return fail(c, RRTE_INVALID_ARG, "unknown mode %u", p->mode);
+    if (p->jitter > RRTE_JITTER_RANDOM) return fail(c, RRTE_INVALID_ARG, "unknown jitter %u", p->jitter);
+    // (the high bits are the library's own per-launch flags, kFlagSlabRgb24 / kFlagHostStore)
+    if (p->flags & ~(uint32_t)(RRTE_FLAG_F32_LINEAR | RRTE_FLAG_GATHER_OVERLAP))
+        return fail(c, RRTE_INVALID_ARG, "unknown flags 0x%x", p->flags);
+    return validate_scene(c, s);
 }
 
 // Conservative world-space bounding sphere of one object for wave culling
@@ -2202,7 +2211,7 @@ void rrte_hip_destroy(rrte_ctx* c) {
         if (B.ev_up) (void)hipEventDestroy(B.ev_up);
         destroy_events(B.ret);
     }
-    void* bufs[] = {c->d_rgba, c->d_f32, c->d_counters, c->d_gather, c->d_full};
+    void* bufs[] = {c->d_rgba, c->d_f32, c->d_counters, c->d_gather, c->d_full, c->d_qin, c->d_qout};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (void* b : c->graveyard)
@@ -3179,6 +3188,142 @@ rrte_status rrte_hip_render_gather(rrte_ctx* c, const rrte_scene_ir* s, const rr
         c->stats.gather_ms = all_ms - k_ms;
     }
     return finish_frame(c);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- ray queries (include/rrte_hip_query.h)
+// Closest hit, any hit and pixel picking over the cached scene (kernel: ray_query.hpp).  Local
+// calls: no collective, no gather-batch close, rrte_stats untouched.
+namespace {
+
+// Rays per launch of the blocking forms: bounds the context's staging buffers (128 MiB of rays,
+// 192 MiB of hits) however large the call is.
+constexpr uint32_t kQueryChunk = 1u << 22;
+
+// The scene of a query, cached and readable on `st`: validated, uploaded through the context's scene
+// cache if it differs from the cached one, `st` ordered after the version's upload and registered with
+// its retire tracking (as issue_launch does for a frame).
+rrte_status query_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st) {
+    rrte_status r = validate_scene(c, s);
+    if (r != RRTE_OK) return r;
+    const uint64_t renders = c->same_scene_renders;
+    double up = 0.0;
+    if ((r = upload_scene(c, s, st, &up)) != RRTE_OK) return r;
+    // a query of the cached scene is not a render of it (JIT AUTO counts consecutive renders)
+    if (c->same_scene_renders == renders + 1) c->same_scene_renders = renders;
+    if (c->sb_cur >= 0) {
+        rrte_ctx::SceneBuf& B = c->sb[c->sb_cur];
+        if (std::find(B.ordered.begin(), B.ordered.end(), st) == B.ordered.end()) {
+            HIPCHK(c, ev_wait(c, st, B.ev_up, "wait scene upload"));
+            B.ordered.push_back(st);
+        }
+        B.ret.use(st);
+    }
+    c->launched.use(st);
+    return RRTE_OK;
+}
+
+// Enqueue one query launch of n rays (or n pixel pairs with `qc`) on `st`.
+rrte_status query_launch(rrte_ctx* c, const rrte_scene_ir* s, const void* d_in, uint32_t n, uint32_t flags,
+                         const QueryCam* qc, void* d_hits, hipStream_t st) {
+    const SceneView sv{c->d_prims, c->d_mats, c->d_lights, c->d_nodes, s->num_prims, s->num_lights, s->num_materials,
+                       c->mesh_view};
+    const uint32_t need = c->env_generic_all ? kFeatAll : c->scene_feat;
+    static const QueryCam no_cam{};
+    trace_rec(c, "launch query", st, nullptr, n, flags);
+    if (qc)
+        launch_query<false, true>(need, n, st, sv, d_in, *qc, d_hits);
+    else if (flags & RRTE_QUERY_ANY)
+        launch_query<true, false>(need, n, st, sv, d_in, no_cam, d_hits);
+    else
+        launch_query<false, false>(need, n, st, sv, d_in, no_cam, d_hits);
+    HIPCHK(c, hipGetLastError());
+    return RRTE_OK;
+}
+
+// The blocking forms: `in_stride` bytes per ray (or pixel pair) staged through the context's buffers
+// in chunks on the context's stream; returns after the hits are on the host.
+rrte_status query_blocking(rrte_ctx* c, const rrte_scene_ir* s, const void* in, size_t in_stride, uint32_t n,
+                           uint32_t flags, const QueryCam* qc, rrte_ray_hit* hits) {
+    rrte_status r = query_scene(c, s, c->stream);
+    if (r != RRTE_OK) return r;
+    const uint32_t chunk = std::min(n, kQueryChunk);
+    if ((r = ensure(c, c->d_qin, c->cap_qin, (size_t)chunk * in_stride)) != RRTE_OK) return r;
+    if ((r = ensure(c, c->d_qout, c->cap_qout, (size_t)chunk * sizeof(rrte_ray_hit))) != RRTE_OK) return r;
+    for (uint32_t done = 0; done < n; done += chunk) {
+        const uint32_t m = std::min(chunk, n - done);
+        HIPCHK(c, hipMemcpyAsync(c->d_qin, static_cast<const uint8_t*>(in) + (size_t)done * in_stride,
+                                 (size_t)m * in_stride, hipMemcpyHostToDevice, c->stream));
+        if ((r = query_launch(c, s, c->d_qin, m, flags, qc, c->d_qout, c->stream)) != RRTE_OK) return r;
+        HIPCHK(c, hipMemcpyAsync(hits + done, c->d_qout, (size_t)m * sizeof(rrte_ray_hit), hipMemcpyDeviceToHost,
+                                 c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RRTE_OK;
+}
+
+rrte_status query_args(rrte_ctx* c, const rrte_scene_ir* s, const void* in, uint32_t n, uint32_t flags,
+                       const void* out) {
+    if (!s || !in || !out) return fail(c, RRTE_INVALID_ARG, "null scene, ray or hit buffer");
+    if (n == 0 || n > RRTE_QUERY_MAX_RAYS) return fail(c, RRTE_INVALID_ARG, "ray count %u outside [1, 2^24]", n);
+    if (flags & ~RRTE_QUERY_ANY) return fail(c, RRTE_INVALID_ARG, "unknown query flags 0x%x", flags);
+    return RRTE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+rrte_status rrte_hip_raycast(rrte_ctx* c, const rrte_scene_ir* s, const rrte_ray* rays, uint32_t n, uint32_t flags,
+                             rrte_ray_hit* hits_out) {
+    if (!c) return RRTE_INVALID_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    rrte_status r = query_args(c, s, rays, n, flags, hits_out);
+    if (r != RRTE_OK) return r;
+    return query_blocking(c, s, rays, sizeof(rrte_ray), n, flags, nullptr, hits_out);
+}
+
+rrte_status rrte_hip_raycast_async(rrte_ctx* c, const rrte_scene_ir* s, const void* d_rays, uint32_t n, uint32_t flags,
+                                   void* d_hits, void* stream) {
+    if (!c) return RRTE_INVALID_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    rrte_status r = query_args(c, s, d_rays, n, flags, d_hits);
+    if (r != RRTE_OK) return r;
+    if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u)
+        return fail(c, RRTE_INVALID_ARG, "device ray and hit buffers must be 16-byte aligned");
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    if ((r = query_scene(c, s, st)) != RRTE_OK) return r;
+    return query_launch(c, s, d_rays, n, flags, nullptr, d_hits, st);
+}
+
+rrte_status rrte_hip_pick(rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_params* p, const uint32_t* xy,
+                          uint32_t n, rrte_ray_hit* hits_out) {
+    if (!c) return RRTE_INVALID_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!p) return fail(c, RRTE_INVALID_ARG, "null params");
+    rrte_status r = query_args(c, s, xy, n, RRTE_QUERY_CLOSEST, hits_out);
+    if (r != RRTE_OK) return r;
+    if (p->width == 0 || p->height == 0) return fail(c, RRTE_INVALID_ARG, "zero-sized frame %ux%u", p->width, p->height);
+    if ((uint64_t)p->width * p->height > (1ull << 30)) return fail(c, RRTE_INVALID_ARG, "frame too large");
+    for (uint32_t i = 0; i < n; ++i)
+        if (xy[2 * (size_t)i] >= p->width || xy[2 * (size_t)i + 1] >= p->height)
+            return fail(c, RRTE_INVALID_ARG, "pixel %u (%u, %u) outside the %ux%u frame", i, xy[2 * (size_t)i],
+                        xy[2 * (size_t)i + 1], p->width, p->height);
+    // the frame's camera record (make_params), for a frame of this size
+    rrte_render_params pf{};
+    pf.width = p->width;
+    pf.height = p->height;
+    pf.samples_per_pixel = 1;
+    pf.gamma = 2.2f;
+    pf.t_min = p->t_min;
+    const KParams k = make_params(c, s, &pf, p->height);
+    QueryCam qc{};
+    qc.cam = k.cam[0];
+    qc.width = p->width;
+    qc.height = p->height;
+    qc.t_min = p->t_min;
+    return query_blocking(c, s, xy, 2 * sizeof(uint32_t), n, RRTE_QUERY_CLOSEST, &qc, hits_out);
 }
 
 }  // extern "C"

@@ -933,5 +933,74 @@ class Raytracer:
                                               outf.ctypes.data if outf is not None else None))
         return out8, outf
 
+    # ------------------------------------------------------- ray queries (include/rrte_hip_query.h)
+    def raycast(self, objects, origins, directions, t_min=1e-3, t_max=math.inf, any_hit=False, lights=()) -> np.ndarray:
+        """One ray per row of `origins` / `directions` ((n, 3); directions need not be unit length)
+        over [t_min, t_max] (scalars or (n,) arrays, t along the normalised direction): the closest
+        hit of each (ray_color's search, raytracer.rs:103-113) or, with any_hit, the first object in
+        list order that occludes it.  Returns n records of abi.RAY_HIT_DTYPE (prim = -1: miss).
+        `lights`: the lights the scene is rendered with, so that a query between frames of the same
+        scene finds it cached on the device (lights are part of the cached scene)."""
+        rays = self.make_rays(origins, directions, t_min, t_max)
+        hits = np.zeros(len(rays), dtype=abi.RAY_HIT_DTYPE)
+        scene = LoweredScene(objects, lights, Camera())
+        ctx = self.ctx
+        ctx.check(ctx.lib.rrte_hip_raycast(ctx.h, scene.ref(), rays.ctypes.data_as(C.POINTER(abi.Ray)), len(rays),
+                                           abi.QUERY_ANY if any_hit else abi.QUERY_CLOSEST,
+                                           hits.ctypes.data_as(C.POINTER(abi.RayHit))))
+        return hits
+
+    def raycast_async(self, objects, d_rays: int, n: int, d_hits: int, stream: int | None = None, any_hit=False,
+                      lights=()):
+        """rrte_hip_raycast_async: n abi.RAY_DTYPE records at device address `d_rays` in, n
+        abi.RAY_HIT_DTYPE records at device address `d_hits` out (both 16-byte aligned), enqueued on
+        `stream` (a hipStream_t as an integer; None = the context's stream).  Returns at once; the
+        stream must stay valid until the context is next synchronised."""
+        scene = LoweredScene(objects, lights, Camera())
+        ctx = self.ctx
+        ctx.check(ctx.lib.rrte_hip_raycast_async(ctx.h, scene.ref(), d_rays, n,
+                                                 abi.QUERY_ANY if any_hit else abi.QUERY_CLOSEST, d_hits, stream))
+
+    @staticmethod
+    def make_rays(origins, directions, t_min=1e-3, t_max=math.inf) -> np.ndarray:
+        """(n, 3) origins and directions and their interval as n records of abi.RAY_DTYPE."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("origins and directions differ in length")
+        rays = np.zeros(len(o), dtype=abi.RAY_DTYPE)
+        rays["origin"], rays["direction"] = o, d
+        rays["t_min"] = np.asarray(t_min, dtype=np.float32)
+        rays["t_max"] = np.asarray(t_max, dtype=np.float32)
+        return rays
+
+    def pick(self, objects, camera: Camera, xs, ys, lights=()) -> np.ndarray:
+        """The closest hit under each pixel (xs[i], ys[i]) of the configured width x height frame seen
+        by `camera`: the frame's own pixel-centre primary ray (jitter "center"), t_min = config.t_min.
+        Returns records of abi.RAY_HIT_DTYPE; a pixel outside the frame raises (INVALID_ARG)."""
+        xy = np.ascontiguousarray(np.stack([np.asarray(xs).reshape(-1), np.asarray(ys).reshape(-1)], axis=1),
+                                  dtype=np.uint32)
+        hits = np.zeros(len(xy), dtype=abi.RAY_HIT_DTYPE)
+        scene = LoweredScene(objects, lights, camera)
+        prm = self.config.lower()
+        ctx = self.ctx
+        ctx.check(ctx.lib.rrte_hip_pick(ctx.h, scene.ref(), C.byref(prm), xy.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        len(xy), hits.ctypes.data_as(C.POINTER(abi.RayHit))))
+        return hits
+
+    @staticmethod
+    def hit_objects(objects, hits) -> list:
+        """The Python object behind each hit record: None for a miss, the object, or for a Mesh the
+        pair (mesh, triangle index in the mesh's own index order)."""
+        from .mesh import Mesh
+        out = []
+        for prim, tri in zip(np.asarray(hits["prim"]).reshape(-1), np.asarray(hits["tri"]).reshape(-1)):
+            if prim < 0:
+                out.append(None)
+            else:
+                o = objects[int(prim)]
+                out.append((o, int(tri)) if isinstance(o, Mesh) else o)
+        return out
+
     def stats(self) -> abi.Stats:
         return self.ctx.stats()

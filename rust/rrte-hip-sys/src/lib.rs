@@ -162,3 +162,5 @@ extern "C" {
 }
 
 pub mod safe;
+// ray queries (include/rrte_hip_query.h): their own extern block, records and safe wrappers
+pub mod query;

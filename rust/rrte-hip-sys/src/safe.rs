@@ -49,7 +49,7 @@ pub struct SceneIr {
 
 impl SceneIr {
     /// The C view of the arrays; valid while `self` is neither moved nor modified.
-    fn raw(&self) -> rrte_scene_ir {
+    pub(crate) fn raw(&self) -> rrte_scene_ir {
         rrte_scene_ir {
             prims: self.prims.as_ptr(),
             num_prims: self.prims.len() as u32,
@@ -103,7 +103,7 @@ impl Drop for PageBuf {
 
 /// One rrte_hip context on one HIP device.
 pub struct Context {
-    ctx: *mut rrte_ctx,
+    pub(crate) ctx: *mut rrte_ctx,
     // a frame buffer the context owns and keeps pinned (rrte_hip_host_register): render_pinned has the
     // kernel store each frame straight into it (no D2H copy after the render)
     frame: Option<PageBuf>,
@@ -131,7 +131,7 @@ impl Context {
         Ok(Self { ctx, frame: None, pinned: None, unpinnable: 0 })
     }
 
-    fn check(&self, st: rrte_status) -> Result<(), Error> {
+    pub(crate) fn check(&self, st: rrte_status) -> Result<(), Error> {
         if st == RRTE_OK {
             return Ok(());
         }
