@@ -272,6 +272,18 @@ public:
     std::vector<uint32_t> indices;
 };
 
+// A Mesh placed in the world through a transform (RRTE_PRIM_MESH_INSTANCE, include/rrte_hip.h): the
+// mesh's triangle range and BVH are stored once, however many instances (and the mesh itself) a scene
+// holds, and moving, rotating or scaling the instance changes only its transform.  The scale may be
+// non-uniform or mirrored, not zero.  The material defaults to the mesh's.
+class MeshInstance : public SceneObject {
+public:
+    explicit MeshInstance(std::shared_ptr<Mesh> mesh, const Transform& transform = Transform(),
+                          std::shared_ptr<Material> m = nullptr);
+    rrte_prim lower(Lowering&) const override;
+    std::shared_ptr<Mesh> mesh;
+};
+
 // ----------------------------------------------------- SDF / CSG / deformers (README.md:458-510)
 struct Bound {
     double c[3];

@@ -61,7 +61,7 @@ typedef enum rrte_prim_kind {
     RRTE_PRIM_CAPSULE = 6,  /* primitives.rs:626-725 p: center[0..2], radius[3], height[4] */
     RRTE_PRIM_SDF = 7,      /* build-defined SDFObject: sphere-traced node program;
                                p: bounding sphere center[0..2], radius[3]                 */
-    RRTE_PRIM_MESH = 8      /* triangle mesh (rrte-assets MeshAsset, asset.rs:53-65): triangles
+    RRTE_PRIM_MESH = 8,     /* triangle mesh (rrte-assets MeshAsset, asset.rs:53-65): triangles
                                sdf_first .. sdf_first+sdf_count-1 of rrte_scene_ir.mesh_indices
                                (3 vertex indices each).  Every triangle is Triangle::intersect
                                (primitives.rs:208-244) with set_normals(n0,n1,n2) -- the vertex
@@ -71,6 +71,35 @@ typedef enum rrte_prim_kind {
                                object list.  Like Triangle it ignores trs (bake the entity
                                transform into the vertices).  The device traverses a BVH built
                                once per scene; see DESIGN.md §5.                          */
+    RRTE_PRIM_MESH_INSTANCE = 9
+                            /* a triangle range named exactly as RRTE_PRIM_MESH names it (sdf_first,
+                               sdf_count), placed in the world through trs.  Any number of kind-8 and
+                               kind-9 prims may name the same range: it is stored and its BVH built
+                               once.  Build-defined (the reference has no mesh object)
+                               and deliberately not the Cube's rule, which reports the local ray's t:
+                               an instance's t is in world units.  With r the world ray after
+                               Ray::new and M / inv = Transform::to_matrix / inverse_matrix of trs:
+                                 1. v = m_vector(inv, r.d);
+                                 2. len = the correctly rounded f32 sqrt of vlen2(v), summed in
+                                    vdot's order;
+                                 3. the local ray is local_ray()'s: ray_new(m_point(inv, r.o), vnorm(v));
+                                 4. the local interval is [t_min * len, t_max * len] as f32 products
+                                    (t_max = +inf stays +inf);
+                                 5. the hit is the range's hit for the local ray in that interval by
+                                    RRTE_PRIM_MESH's rule (index order, strict '<', the lower index
+                                    wins; a non-finite local ray takes the original-order scan):
+                                    tl, the triangle, u, v and the interpolated normalised normal
+                                    n_l, before any flip;
+                                 6. reported: t = tl / len (f32 division); point = m_point(M,
+                                    ray_at(local ray, tl)); outward normal = vnorm(n_w) with n_w[j] =
+                                    vdot(column j of inv, n_l) -- the inverse transpose, right under
+                                    non-uniform scale and mirroring; all through HitInfo::new against
+                                    the WORLD ray;
+                                 7. the any-hit form (shadow rays, RRTE_QUERY_ANY) uses the same local
+                                    ray and interval;
+                                 8. rrte_ray_hit.tri is the triangle's index within the range.
+                               RRTE_INVALID_ARG if a scale component is zero or non-finite, the
+                               position or rotation is non-finite, or the range is out of bounds.  */
 } rrte_prim_kind;
 
 /* One SceneObject lowered to POD (192 bytes).  trs is the object's

@@ -19,6 +19,7 @@ RRTE_OK, RRTE_INVALID_ARG, RRTE_HIP_ERROR, RRTE_RCCL_ERROR, RRTE_UNSUPPORTED_PRI
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "HIP_ERROR", 3: "RCCL_ERROR", 4: "UNSUPPORTED_PRIM", 5: "NO_DEVICE"}
 
 PRIM_SPHERE, PRIM_PLANE, PRIM_TRIANGLE, PRIM_CUBE, PRIM_CYLINDER, PRIM_CONE, PRIM_CAPSULE, PRIM_SDF, PRIM_MESH = range(9)
+PRIM_MESH_INSTANCE = 9  # a mesh range placed through trs (include/rrte_hip.h)
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_EMISSIVE = range(4)
 LIGHT_POINT, LIGHT_DIRECTIONAL, LIGHT_SPOT, LIGHT_AMBIENT = range(4)
 PERSPECTIVE, ORTHOGRAPHIC = 0, 1
@@ -183,6 +184,19 @@ QUERY_EXPORTS = {
                                 C.POINTER(RayHit)]),
 }
 
+# ------------------------------------------------ mesh sharing diagnostics (include/rrte_hip_mesh.h)
+class MeshInfo(C.Structure):
+    _fields_ = [("bvh_builds", C.c_uint64), ("ranges", C.c_uint32), ("tri_slots", C.c_uint32),
+                ("bvh_nodes", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+assert C.sizeof(MeshInfo) == 24
+
+# Every entry point include/rrte_hip_mesh.h declares.
+MESH_EXPORTS = {
+    "rrte_hip_mesh_info": (C.c_int, [_P, C.POINTER(MeshInfo)]),
+}
+
 _lib = None
 
 
@@ -203,7 +217,7 @@ def load() -> C.CDLL:
     except Exception:
         pass
     lib = C.CDLL(str(LIB_PATH), mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**EXPORTS, **QUERY_EXPORTS}.items():
+    for name, (res, args) in {**EXPORTS, **QUERY_EXPORTS, **MESH_EXPORTS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

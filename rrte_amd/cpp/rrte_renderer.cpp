@@ -190,6 +190,13 @@ public:
     std::vector<rrte_sdf_node> nodes;
     std::vector<rrte_mesh_vertex> mesh_vertices;
     std::vector<uint32_t> mesh_indices;
+    // one Mesh object, one range: added the first time the mesh or one of its instances is lowered
+    std::map<const Mesh*, std::pair<uint32_t, uint32_t>> ranges;
+    std::pair<uint32_t, uint32_t> mesh_range(const Mesh& m) {
+        auto it = ranges.find(&m);
+        if (it == ranges.end()) it = ranges.emplace(&m, add_mesh(m)).first;
+        return it->second;
+    }
     std::pair<uint32_t, uint32_t> add_mesh(const Mesh& m) {
         const uint32_t base = (uint32_t)mesh_vertices.size(), first = (uint32_t)(mesh_indices.size() / 3);
         const size_t nv = m.positions.size() / 3;
@@ -295,7 +302,21 @@ Mesh::Mesh(std::vector<float> pos, std::vector<uint32_t> idx, std::vector<float>
 }
 rrte_prim Mesh::lower(Lowering& lw) const {
     rrte_prim r = prim(RRTE_PRIM_MESH, {});
-    const auto fc = lw.add_mesh(*this);
+    const auto fc = lw.mesh_range(*this);
+    r.sdf_first = fc.first;
+    r.sdf_count = fc.second;
+    return r;
+}
+
+MeshInstance::MeshInstance(std::shared_ptr<Mesh> mesh_, const Transform& transform, std::shared_ptr<Material> m)
+    : mesh(std::move(mesh_)) {
+    if (!mesh) throw Error(RRTE_INVALID_ARG, "mesh instance of no mesh");
+    transform_ = transform;
+    material_ = m ? std::move(m) : mesh->material();
+}
+rrte_prim MeshInstance::lower(Lowering& lw) const {
+    rrte_prim r = prim(RRTE_PRIM_MESH_INSTANCE, {});
+    const auto fc = lw.mesh_range(*mesh);
     r.sdf_first = fc.first;
     r.sdf_count = fc.second;
     return r;

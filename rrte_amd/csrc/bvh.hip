@@ -175,12 +175,21 @@ inline float bits_f(uint32_t u) {
 
 }  // namespace
 
-void build_mesh_bvhs(const rrte_scene_ir* s, DPrim* prims, MeshData& out, float4* bounds) {
+std::vector<std::pair<uint32_t, uint32_t>> mesh_ranges_of(const rrte_scene_ir* s) {
+    std::vector<std::pair<uint32_t, uint32_t>> out;
     for (uint32_t pi = 0; pi < s->num_prims; ++pi) {
         const rrte_prim& in = s->prims[pi];
-        if (in.kind != RRTE_PRIM_MESH) continue;
-        const uint32_t ntri = in.sdf_count;
-        const uint32_t* ix = s->mesh_indices + (size_t)in.sdf_first * 3;
+        if (in.kind != RRTE_PRIM_MESH && in.kind != RRTE_PRIM_MESH_INSTANCE) continue;
+        const std::pair<uint32_t, uint32_t> key(in.sdf_first, in.sdf_count);
+        if (std::find(out.begin(), out.end(), key) == out.end()) out.push_back(key);
+    }
+    return out;
+}
+
+void build_mesh_ranges(const rrte_scene_ir* s, MeshData& out) {
+    for (const auto& key : mesh_ranges_of(s)) {
+        const uint32_t ntri = key.second;
+        const uint32_t* ix = s->mesh_indices + (size_t)key.first * 3;
         const rrte_mesh_vertex* vx = s->mesh_vertices;
         std::vector<BTri> tris(ntri);
         for (uint32_t k = 0; k < ntri; ++k) {
@@ -220,23 +229,78 @@ void build_mesh_bvhs(const rrte_scene_ir* s, DPrim* prims, MeshData& out, float4
             out.norms.push_back(f4(v2.normal[0], v2.normal[1], v2.normal[2], 0.0f));
             out.perm[slot_base + o] = slot_base + k;
         }
+        MeshRange mr{};
+        mr.first = key.first;
+        mr.count = ntri;
+        mr.root = ntri ? glob(root.first) : kLeafBit;  // root link (an empty mesh: no triangles at all)
+        mr.slot_base = slot_base;
+        for (int a = 0; a < 3; ++a) {
+            mr.lo[a] = root.second.lo[a];
+            mr.hi[a] = root.second.hi[a];
+        }
+        out.ranges.push_back(mr);
+    }
+}
+
+float4 sphere_bound(const double c_in[3], double r, const float* xf) {
+    const double inf = __builtin_huge_val();
+    double c[3] = {c_in[0], c_in[1], c_in[2]};
+    if (xf && r < inf) {  // p' = M p: centre through xf, radius by the largest column norm
+        double w[3];
+        for (int k = 0; k < 3; ++k)
+            w[k] = (double)xf[0 + k] * c[0] + (double)xf[3 + k] * c[1] + (double)xf[6 + k] * c[2] + xf[9 + k];
+        double sn = 0.0;
+        for (int col = 0; col < 3; ++col) {
+            double a = xf[col * 3], b = xf[col * 3 + 1], e = xf[col * 3 + 2];
+            sn = fmax(sn, sqrt(a * a + b * b + e * e));
+        }
+        r *= sn * (1.0 + 1e-5);  // M = R*S (mat4_srt): orthogonal columns, so |M v| <= max column norm * |v|
+        c[0] = w[0]; c[1] = w[1]; c[2] = w[2];
+    }
+    double mag = fmax(fabs(c[0]), fmax(fabs(c[1]), fabs(c[2])));
+    r = r * 1.001 + 1e-3 + 1e-5 * mag;
+    if (!(r < 3e38) || !std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]))
+        return make_float4(0.0f, 0.0f, 0.0f, __builtin_huge_valf());
+    return make_float4((float)c[0], (float)c[1], (float)c[2], nextafterf((float)r, __builtin_huge_valf()));
+}
+
+void assign_mesh_prims(const rrte_scene_ir* s, const MeshData& md, DPrim* prims, float4* bounds) {
+    for (uint32_t pi = 0; pi < s->num_prims; ++pi) {
+        const rrte_prim& in = s->prims[pi];
+        if (in.kind != RRTE_PRIM_MESH && in.kind != RRTE_PRIM_MESH_INSTANCE) continue;
+        const MeshRange* mr = nullptr;
+        for (const MeshRange& m : md.ranges)
+            if (m.first == in.sdf_first && m.count == in.sdf_count) {
+                mr = &m;
+                break;
+            }
+        if (!mr) continue;  // (the caller built md for this scene's ranges, or checked that it holds them)
         DPrim& d = prims[pi];
-        d.sdf_first = ntri ? glob(root.first) : kLeafBit;  // root link (an empty mesh: no triangles at all)
+        const uint32_t ntri = mr->count;
+        d.sdf_first = mr->root;
         d.sdf_count = ntri;
-        d.p[0] = (float)slot_base;
+        d.p[0] = (float)mr->slot_base;
         if (bounds) {
-            const Box& b = root.second;
             double c[3], r2 = 0.0;
             for (int a = 0; a < 3; ++a) {
-                c[a] = 0.5 * ((double)b.lo[a] + b.hi[a]);
-                const double h = 0.5 * ((double)b.hi[a] - b.lo[a]);
+                c[a] = 0.5 * (mr->lo[a] + mr->hi[a]);
+                const double h = 0.5 * (mr->hi[a] - mr->lo[a]);
                 r2 += h * h;
+            }
+            if (in.kind == RRTE_PRIM_MESH_INSTANCE) {
+                bounds[pi] = ntri ? sphere_bound(c, std::sqrt(r2), d.xf) : f4(0.0f, 0.0f, 0.0f, 0.0f);
+                continue;
             }
             const double r = ntri ? std::sqrt(r2) * 1.001 + 1e-3 : 0.0;
             bounds[pi] = (ntri && std::isfinite(r)) ? f4((float)c[0], (float)c[1], (float)c[2], std::nextafter((float)r, INFINITY))
                                                      : f4(0.0f, 0.0f, 0.0f, ntri ? INFINITY : 0.0f);
         }
     }
+}
+
+void build_mesh_bvhs(const rrte_scene_ir* s, DPrim* prims, MeshData& out, float4* bounds) {
+    build_mesh_ranges(s, out);
+    assign_mesh_prims(s, out, prims, bounds);
 }
 
 }  // namespace rrte

@@ -44,6 +44,11 @@ constexpr uint32_t kFeatDeform = 2u;    // SDF programs with deformers (bend, tw
 constexpr uint32_t kFeatAnalytic = 4u;  // plane, triangle, cube, cylinder, cone, capsule
 constexpr uint32_t kFeatSdf = 8u;       // SDF objects
 constexpr uint32_t kFeatAll = 15u;
+// RRTE_PRIM_MESH_INSTANCE objects (a mesh range placed through xf/inv).  Not part of kFeatAll: only a
+// scene that holds an instance runs a variant with the instance path, so every other scene keeps the
+// kernels (and their register budgets) it had before instances existed.
+constexpr uint32_t kFeatInstance = 16u;
+constexpr uint32_t kFeatEvery = kFeatAll | kFeatInstance;
 
 struct SceneView {
     static constexpr bool kStatic = false;
@@ -1312,17 +1317,26 @@ __device__ __forceinline__ bool mt_test(f3 v0, f3 e1, f3 e2, const Ray& r, float
 
 __device__ __forceinline__ f3 xyz(float4 a) { return V(a.x, a.y, a.z); }
 
-// Hit attributes of triangle slot k: re-run the test for (u, v), barycentric normal
-// (primitives.rs:240-243), HitInfo::new.
-__device__ __forceinline__ bool mesh_tri_hit(const MeshView& mv, uint32_t k, const Ray& r, float t_min, float t_max,
-                                             Hit& out) {
-    float t, u, v;
+// Triangle slot k against r: re-run the test for (u, v); t and the barycentric normal
+// (primitives.rs:240-243), normalised, not yet flipped towards the ray.
+__device__ __forceinline__ bool mesh_tri_local(const MeshView& mv, uint32_t k, const Ray& r, float t_min, float t_max,
+                                               float& t, f3& n) {
+    float u, v;
     if (!mt_test(xyz(mv.tris[3 * k]), xyz(mv.tris[3 * k + 1]), xyz(mv.tris[3 * k + 2]), r, t_min, t_max, t, u, v))
         return false;
-    f3 p = ray_at(r, t);
     float w = 1.0f - u - v;
-    f3 n = vnorm(vadd(vadd(vmuls(xyz(mv.norms[3 * k]), w), vmuls(xyz(mv.norms[3 * k + 1]), u)),
-                      vmuls(xyz(mv.norms[3 * k + 2]), v)));
+    n = vnorm(vadd(vadd(vmuls(xyz(mv.norms[3 * k]), w), vmuls(xyz(mv.norms[3 * k + 1]), u)),
+                   vmuls(xyz(mv.norms[3 * k + 2]), v)));
+    return true;
+}
+
+// Hit attributes of triangle slot k: mesh_tri_local, then HitInfo::new.
+__device__ __forceinline__ bool mesh_tri_hit(const MeshView& mv, uint32_t k, const Ray& r, float t_min, float t_max,
+                                             Hit& out) {
+    float t;
+    f3 n;
+    if (!mesh_tri_local(mv, k, r, t_min, t_max, t, n)) return false;
+    f3 p = ray_at(r, t);
     hit_new(out, t, p, n, r);
     out.sub = k;
     return true;
@@ -1437,6 +1451,49 @@ __device__ __forceinline__ bool isect_mesh(const DPrim& pr, const MeshView& mv, 
     return found;
 }
 
+// ------------------------------------------------------- mesh instances
+// RRTE_PRIM_MESH_INSTANCE (rrte_hip.h): the object-space ray of local_ray(), the length `len` the
+// direction had before it was normalised, and the world interval in local units.  t along the local
+// ray is len times t along the world ray, so the hit's t goes back as tl / len: in world units,
+// comparable with every other object's.
+struct InstanceRay {
+    Ray lr;
+    float len, t_min, t_max;
+};
+__device__ __forceinline__ InstanceRay instance_ray(const DPrim& pr, const Ray& r, float t_min, float t_max) {
+    InstanceRay ir;
+    const f3 v = m_vector(pr.inv, r.d);
+    ir.len = sqrt_rn(vlen2(v));
+    ir.lr = ray_new(m_point(pr.inv, r.o), vnorm(v));
+    ir.t_min = t_min * ir.len;
+    ir.t_max = t_max == kInf ? kInf : t_max * ir.len;
+    return ir;
+}
+
+template <bool ANY>
+__device__ __forceinline__ bool isect_mesh_instance(const DPrim& pr, const MeshView& mv, const Ray& r, float t_min,
+                                                    float t_max, Hit& out) {
+    const InstanceRay ir = instance_ray(pr, r, t_min, t_max);
+    if (!isect_mesh<ANY>(pr, mv, ir.lr, ir.t_min, ir.t_max, out)) return false;
+    out.t = out.t / ir.len;
+    return true;
+}
+
+// Hit attributes of an instance's triangle slot k: the slot's test on the local ray over the local
+// interval, the point through xf, the normal through the inverse transpose (n_w[j] = column j of
+// inv . n_l: right under non-uniform scale and mirroring), HitInfo::new against the world ray.
+__device__ __forceinline__ bool mesh_instance_hit(const DPrim& pr, const MeshView& mv, uint32_t k, const Ray& r,
+                                                  float t_min, float t_max, Hit& out) {
+    const InstanceRay ir = instance_ray(pr, r, t_min, t_max);
+    float tl;
+    f3 nl;
+    if (!mesh_tri_local(mv, k, ir.lr, ir.t_min, ir.t_max, tl, nl)) return false;
+    const f3 nw = V(vdot(vld(pr.inv), nl), vdot(vld(pr.inv + 3), nl), vdot(vld(pr.inv + 6), nl));
+    hit_new(out, tl / ir.len, m_point(pr.xf, ray_at(ir.lr, tl)), vnorm(nw), r);
+    out.sub = k;
+    return true;
+}
+
 // SceneObject::intersect dispatch, runtime object index: switch on the kind
 // (wave-uniform -> scalar branches).
 template <bool NEED_HIT, class S, bool ANY = false>
@@ -1478,6 +1535,8 @@ __device__ __forceinline__ bool intersect_at(const S& sc, uint32_t i, const Ray&
     }
     if constexpr ((F & kFeatMesh) != 0u)
         if (pr.kind == RRTE_PRIM_MESH) return isect_mesh<ANY>(pr, sc.mesh, r, t_min, t_max, out);
+    if constexpr ((F & kFeatInstance) != 0u)
+        if (pr.kind == RRTE_PRIM_MESH_INSTANCE) return isect_mesh_instance<ANY>(pr, sc.mesh, r, t_min, t_max, out);
     return false;
 }
 
@@ -1520,6 +1579,8 @@ __device__ __forceinline__ bool intersect_at(const S& sc, UC<I> ii, const Ray& r
                          (ANY ? kSecantExit >= 1 : kSecantExit >= 2) && prim_convex<S, I>()>(
             pr, SdfStaticProgram<S, prim_first<S, I>(), prim_count<S, I>()>{sc}, r, t_min, t_max, out);
     else if constexpr (kind == RRTE_PRIM_MESH) return isect_mesh<ANY>(pr, sc.mesh, r, t_min, t_max, out);
+    else if constexpr (kind == RRTE_PRIM_MESH_INSTANCE)
+        return isect_mesh_instance<ANY>(pr, sc.mesh, r, t_min, t_max, out);
     else return false;
 }
 
@@ -1592,6 +1653,12 @@ __device__ __forceinline__ void attributes_at(const S& sc, uint32_t i, const Ray
             return;
         }
     }
+    if constexpr ((F & kFeatInstance) != 0u) {
+        if (pr.kind == RRTE_PRIM_MESH_INSTANCE) {
+            mesh_instance_hit(pr, sc.mesh, sub, r, t_min, kInf, out);
+            return;
+        }
+    }
     if constexpr ((F & kFeatAnalytic) != 0u) intersect_at<true>(sc, i, r, t_min, kInf, out);
 }
 template <class S, uint32_t I>
@@ -1602,6 +1669,8 @@ __device__ __forceinline__ void attributes_at(const S& sc, UC<I> ii, const Ray& 
         sdf_hit_attributes(SdfStaticProgram<S, prim_first<S, I>(), prim_count<S, I>()>{sc}, r, t, out);
     else if constexpr (kind == RRTE_PRIM_MESH)
         mesh_tri_hit(sc.mesh, sub, r, t_min, kInf, out);
+    else if constexpr (kind == RRTE_PRIM_MESH_INSTANCE)
+        mesh_instance_hit(prim_at(sc, ii), sc.mesh, sub, r, t_min, kInf, out);
     else if constexpr (kind == RRTE_PRIM_SPHERE)
         sphere_attributes(prim_at(sc, ii), r, t, out);
     else

@@ -73,6 +73,13 @@ __device__ __forceinline__ void query_attributes(const S& sc, uint32_t i, const 
             return;
         }
     }
+    if constexpr ((F & kFeatInstance) != 0u) {
+        if (pr.kind == RRTE_PRIM_MESH_INSTANCE) {
+            mesh_instance_hit(pr, sc.mesh, sub, r, t_min, t_max, out);
+            tri = __float_as_uint(sc.mesh.tris[3u * sub].w);
+            return;
+        }
+    }
     if constexpr ((F & kFeatAnalytic) != 0u) intersect_at<true>(sc, i, r, t_min, t_max, out);
 }
 
@@ -173,8 +180,10 @@ inline void launch_query(uint32_t need, uint32_t n, hipStream_t st, const SceneV
         hipLaunchKernelGGL((ray_query_kernel<ANY, PICK, kFeatAnalytic>), grid, block, 0, st, sv, in, n, qc, out);
     else if ((need & ~kFeatSdf) == 0u)
         hipLaunchKernelGGL((ray_query_kernel<ANY, PICK, kFeatSdf>), grid, block, 0, st, sv, in, n, qc, out);
-    else
+    else if ((need & kFeatInstance) == 0u)
         hipLaunchKernelGGL((ray_query_kernel<ANY, PICK, kFeatAll>), grid, block, 0, st, sv, in, n, qc, out);
+    else
+        hipLaunchKernelGGL((ray_query_kernel<ANY, PICK, kFeatEvery>), grid, block, 0, st, sv, in, n, qc, out);
 }
 
 }  // namespace rrte

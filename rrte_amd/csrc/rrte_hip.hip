@@ -29,6 +29,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../include/rrte_hip_mesh.h"
 #include "bvh.hpp"
 #include "jit.hpp"
 #include "sdf_guard.hpp"
@@ -230,6 +231,12 @@ struct rrte_ctx {
     int emu_peers = 0;
     uint64_t scene_gen = 0;       // bumped whenever the cached scene changes
     uint32_t scene_feat = kFeatAll;  // the cached scene's features (kFeat*): its generic kernel variant
+    // The last built mesh data (one entry), kept on the host so that a scene change that leaves the mesh
+    // arrays and the set of ranges alone re-uploads it without a BVH build (upload_scene)
+    MeshData mesh_cache;
+    std::vector<unsigned char> mesh_cache_key;  // MeshKey, then the arrays' content when mesh_version is 0
+    bool mesh_cache_valid = false;
+    uint64_t bvh_builds = 0;  // distinct ranges built since the context was created (rrte_hip_mesh_info)
     bool env_generic_all = false;    // RRTE_GENERIC_ALL=1: the all-features generic kernel for every scene (A/B, tests)
     // Batched gathers render the batch's frames in multi-frame launches at its close (default), or with
     // RRTE_BATCH_LAUNCH=0 each frame at its call (its own launch on the caller's stream: the root in
@@ -602,10 +609,18 @@ rrte_status validate_scene(rrte_ctx* c, const rrte_scene_ir* s) {
     if (s->num_mesh_indices / 3 >= (1u << 24)) return fail(c, RRTE_INVALID_ARG, "more than 2^24 mesh triangles");
     for (uint32_t i = 0; i < s->num_prims; ++i) {
         const rrte_prim& pr = s->prims[i];
-        if (pr.kind > RRTE_PRIM_MESH) return fail(c, RRTE_UNSUPPORTED_PRIM, "prim %u: unknown kind %u", i, pr.kind);
-        if (pr.kind == RRTE_PRIM_MESH) {
+        if (pr.kind > RRTE_PRIM_MESH_INSTANCE)
+            return fail(c, RRTE_UNSUPPORTED_PRIM, "prim %u: unknown kind %u", i, pr.kind);
+        if (pr.kind == RRTE_PRIM_MESH || pr.kind == RRTE_PRIM_MESH_INSTANCE) {
             if ((uint64_t)pr.sdf_first + pr.sdf_count > s->num_mesh_indices / 3)
                 return fail(c, RRTE_INVALID_ARG, "prim %u: mesh triangle range out of bounds", i);
+        }
+        if (pr.kind == RRTE_PRIM_MESH_INSTANCE) {
+            for (int k = 0; k < 10; ++k)
+                if (!std::isfinite(pr.trs[k]))
+                    return fail(c, RRTE_INVALID_ARG, "prim %u: mesh instance transform is not finite", i);
+            if (pr.trs[7] == 0.0f || pr.trs[8] == 0.0f || pr.trs[9] == 0.0f)
+                return fail(c, RRTE_INVALID_ARG, "prim %u: mesh instance scale has a zero component", i);
         }
         if (pr.kind == RRTE_PRIM_SDF) {
             if ((uint64_t)pr.sdf_first + pr.sdf_count > s->num_sdf_nodes)
@@ -672,23 +687,7 @@ float4 prim_bound(const rrte_prim& in, const DPrim& d) {
     case RRTE_PRIM_SDF: r = fabs((double)in.p[3]); local = false; break;  // the sphere tracer's own bound
     default: break;                                                       // plane: unbounded
     }
-    if (local && r < inf) {  // p' = M p: centre through xf, radius by the largest column norm
-        double w[3];
-        for (int k = 0; k < 3; ++k)
-            w[k] = (double)d.xf[0 + k] * c[0] + (double)d.xf[3 + k] * c[1] + (double)d.xf[6 + k] * c[2] + d.xf[9 + k];
-        double sn = 0.0;
-        for (int col = 0; col < 3; ++col) {
-            double a = d.xf[col * 3], b = d.xf[col * 3 + 1], e = d.xf[col * 3 + 2];
-            sn = fmax(sn, sqrt(a * a + b * b + e * e));
-        }
-        r *= sn * (1.0 + 1e-5);  // M = R*S (mat4_srt): orthogonal columns, so |M v| <= max column norm * |v|
-        c[0] = w[0]; c[1] = w[1]; c[2] = w[2];
-    }
-    double mag = fmax(fabs(c[0]), fmax(fabs(c[1]), fabs(c[2])));
-    r = r * 1.001 + 1e-3 + 1e-5 * mag;
-    if (!(r < 3e38) || !std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]))
-        return make_float4(0.0f, 0.0f, 0.0f, __builtin_huge_valf());
-    return make_float4((float)c[0], (float)c[1], (float)c[2], nextafterf((float)r, __builtin_huge_valf()));
+    return sphere_bound(c, r, local ? d.xf : nullptr);  // (bvh.hip; mesh objects get theirs from assign_mesh_prims)
 }
 
 // Lower the ABI records to device records (matrices precomputed once per
@@ -831,6 +830,7 @@ uint32_t scene_features(const std::vector<DPrim>& prims, const std::vector<rrte_
     uint32_t f = 0u;
     for (const DPrim& p : prims) {
         if (p.kind == RRTE_PRIM_MESH) f |= kFeatMesh;
+        else if (p.kind == RRTE_PRIM_MESH_INSTANCE) f |= kFeatMesh | kFeatInstance;
         else if (p.kind == RRTE_PRIM_SDF) f |= kFeatSdf;
         else if (p.kind != RRTE_PRIM_SPHERE) f |= kFeatAnalytic;
     }
@@ -850,7 +850,7 @@ __global__ __launch_bounds__(64) void scene_records_check(const DPrim* prims, ui
     if (i >= np) return;
     const DPrim& pr = prims[i];
     uint32_t bad = 0u;
-    if (pr.kind > RRTE_PRIM_MESH) {
+    if (pr.kind > RRTE_PRIM_MESH_INSTANCE) {
         bad |= 16u;
     } else if (pr.kind == RRTE_PRIM_SDF) {
         if ((uint64_t)pr.sdf_first + pr.sdf_count > nn) {
@@ -866,6 +866,23 @@ __global__ __launch_bounds__(64) void scene_records_check(const DPrim* prims, ui
         }
     }
     if (bad) atomicOr(counters + 1, (unsigned long long)bad);
+}
+
+// True if the context's mesh data (rrte_ctx::mesh_cache) was built from the mesh arrays of `s` (kp: its
+// key parts; the mesh identity is parts 4-6) for exactly the ranges the objects of `s` name.
+bool mesh_cache_hit(const rrte_ctx* c, const SceneKeyParts& kp, const rrte_scene_ir* s) {
+    if (!c->mesh_cache_valid) return false;
+    if (c->mesh_cache_key.size() != kp.lens[4] + kp.lens[5] + kp.lens[6]) return false;
+    const unsigned char* k = c->mesh_cache_key.data();
+    for (int i = 4; i < 7; ++i) {
+        if (kp.lens[i] && memcmp(k, kp.parts[i], kp.lens[i])) return false;
+        k += kp.lens[i];
+    }
+    std::vector<std::pair<uint32_t, uint32_t>> want = mesh_ranges_of(s), have;
+    for (const MeshRange& m : c->mesh_cache.ranges) have.emplace_back(m.first, m.count);
+    std::sort(want.begin(), want.end());
+    std::sort(have.begin(), have.end());
+    return want == have;
 }
 
 rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, double* upload_ms) {
@@ -905,9 +922,23 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
     std::vector<float4> bounds;
     lower_scene(s, prims, mats, lights, &bounds);
     lap_up(0);
-    MeshData md;
-    build_mesh_bvhs(s, prims.data(), md, bounds.data());
-    if (md.too_deep) return fail(c, RRTE_UNSUPPORTED_PRIM, "mesh BVH deeper than the traversal stack");
+    // Mesh cache: the mesh data is rebuilt only when the mesh arrays (scene_key_parts' identity) or the
+    // set of ranges the objects name changed; otherwise the last built data is copied into this
+    // scene version as it is (moving an instance, or anything else in the scene, builds no BVH)
+    if (!mesh_cache_hit(c, kparts, s)) {
+        MeshData built;
+        build_mesh_ranges(s, built);
+        if (built.too_deep) return fail(c, RRTE_UNSUPPORTED_PRIM, "mesh BVH deeper than the traversal stack");
+        c->bvh_builds += built.ranges.size();
+        c->mesh_cache = std::move(built);
+        c->mesh_cache_key.clear();
+        for (int i = 4; i < 7; ++i)
+            c->mesh_cache_key.insert(c->mesh_cache_key.end(), static_cast<const unsigned char*>(kparts.parts[i]),
+                                     static_cast<const unsigned char*>(kparts.parts[i]) + kparts.lens[i]);
+        c->mesh_cache_valid = true;
+    }
+    const MeshData& md = c->mesh_cache;
+    assign_mesh_prims(s, md, prims.data(), bounds.data());
     lap_up(1);
     // SDF programs with their exact CSG early-outs (sdf_guard.hpp); the key above stays the caller's IR
     std::vector<rrte_sdf_node> nodes = decorate_scene_sdf(s, c->env_guard_leaves);
@@ -1761,14 +1792,17 @@ rrte_status finish_tile_order(rrte_ctx* c, const LaunchPlan& L, bool profile, hi
 template <int MODE, bool CULL, uint32_t F0, uint32_t F1, uint32_t F2>
 void launch_generic(uint32_t need, dim3 grid, dim3 block, hipStream_t st, const KParams& k, const SceneView& sv,
                     const Cull& cl, uint32_t* d_rgba, float4* d_f32, unsigned long long* ctr) {
+    // (kFeatInstance is in none of F0..F2: an instance scene takes the last branch)
     if ((need & ~F0) == 0u)
         hipLaunchKernelGGL((ray_kernel<MODE, CULL, F0>), grid, block, 0, st, k, sv, cl, d_rgba, d_f32, ctr);
     else if ((need & ~F1) == 0u)
         hipLaunchKernelGGL((ray_kernel<MODE, CULL, F1>), grid, block, 0, st, k, sv, cl, d_rgba, d_f32, ctr);
     else if ((need & ~F2) == 0u)
         hipLaunchKernelGGL((ray_kernel<MODE, CULL, F2>), grid, block, 0, st, k, sv, cl, d_rgba, d_f32, ctr);
-    else
+    else if ((need & kFeatInstance) == 0u)
         hipLaunchKernelGGL((ray_kernel<MODE, CULL, kFeatAll>), grid, block, 0, st, k, sv, cl, d_rgba, d_f32, ctr);
+    else  // a scene with mesh instances: every feature plus the instance path
+        hipLaunchKernelGGL((ray_kernel<MODE, CULL, kFeatEvery>), grid, block, 0, st, k, sv, cl, d_rgba, d_f32, ctr);
 }
 
 // Launch plan `L` (L.k.nframes frames) on `st`; the cached scene is the plan's.
@@ -1815,7 +1849,7 @@ rrte_status issue_launch(rrte_ctx* c, LaunchPlan& L, uint32_t* d_rgba, float4* d
     SceneView sv{c->d_prims, c->d_mats, c->d_lights, c->d_nodes, L.num_prims, L.num_lights, L.num_materials,
                  c->mesh_view};
     const KParams& k = L.k;
-    const uint32_t need = c->env_generic_all ? kFeatAll : c->scene_feat;
+    const uint32_t need = c->env_generic_all ? (kFeatAll | (c->scene_feat & kFeatInstance)) : c->scene_feat;
     if (L.mode == RRTE_MODE_REFCOMPAT)
         launch_generic<RRTE_MODE_REFCOMPAT, false, 0u, kFeatAnalytic, kFeatSdf>(need, grid, block, st, k, sv, cl, d_rgba,
                                                                              d_f32, c->d_counters);
@@ -2348,6 +2382,19 @@ rrte_status rrte_hip_check_word(rrte_ctx* c, uint64_t* word) {
     HIPCHK(c, hipMemcpy(&w, c->d_counters + 1, sizeof w, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemset(c->d_counters + 1, 0, sizeof w));
     *word = w;
+    return RRTE_OK;
+}
+
+// include/rrte_hip_mesh.h
+rrte_status rrte_hip_mesh_info(rrte_ctx* c, rrte_mesh_info* out) {
+    if (!c || !out) return RRTE_INVALID_ARG;
+    memset(out, 0, sizeof *out);
+    out->bvh_builds = c->bvh_builds;
+    if (c->sb_cur >= 0 && c->mesh_cache_valid) {  // (the current scene version holds a copy of the cache)
+        out->ranges = (uint32_t)c->mesh_cache.ranges.size();
+        out->tri_slots = (uint32_t)(c->mesh_cache.tris.size() / 3);
+        out->bvh_nodes = (uint32_t)(c->mesh_cache.nodes.size() / 4);
+    }
     return RRTE_OK;
 }
 
@@ -3229,7 +3276,7 @@ rrte_status query_launch(rrte_ctx* c, const rrte_scene_ir* s, const void* d_in, 
                          const QueryCam* qc, void* d_hits, hipStream_t st) {
     const SceneView sv{c->d_prims, c->d_mats, c->d_lights, c->d_nodes, s->num_prims, s->num_lights, s->num_materials,
                        c->mesh_view};
-    const uint32_t need = c->env_generic_all ? kFeatAll : c->scene_feat;
+    const uint32_t need = c->env_generic_all ? (kFeatAll | (c->scene_feat & kFeatInstance)) : c->scene_feat;
     static const QueryCam no_cam{};
     trace_rec(c, "launch query", st, nullptr, n, flags);
     if (qc)

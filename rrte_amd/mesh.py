@@ -95,7 +95,7 @@ class Mesh:
     def lower(self, lw) -> abi.Prim:
         p = abi.Prim()
         p.kind = abi.PRIM_MESH
-        p.sdf_first, p.sdf_count = lw.add_mesh(self.positions, self.normals, self.indices)
+        p.sdf_first, p.sdf_count = lw.mesh_range(self)
         p.trs[:] = [float(v) for v in self.transform.trs()]
         return p
 
@@ -140,6 +140,44 @@ class Mesh:
                               "color": {"r": 1.0, "g": 1.0, "b": 1.0, "a": 1.0}}
                              for i in range(len(self.positions))],
                 "indices": [int(i) for i in self.indices.reshape(-1)], "metadata": meta}
+
+
+class MeshInstance:
+    """A Mesh placed in the world through a transform (RRTE_PRIM_MESH_INSTANCE): the mesh's triangle
+    range and BVH are stored once, however many instances (and the mesh itself) are in the scene, and
+    moving, rotating or scaling the instance changes only its transform -- no vertices are re-baked
+    and no BVH is rebuilt.  The scale may be non-uniform or mirrored, but not zero.  Hits report t
+    in world units (include/rrte_hip.h spells out the arithmetic)."""
+
+    def __init__(self, mesh: Mesh, transform: Transform | None = None, material=None):
+        self.mesh = mesh
+        self.transform = transform if transform is not None else Transform.identity()
+        self.material = material if material is not None else mesh.material
+        self.name = mesh.name
+
+    # ---- SceneObject surface
+    def set_material(self, material):
+        self.material = material
+
+    def set_transform(self, transform: Transform):
+        self.transform = transform
+
+    @property
+    def num_triangles(self) -> int:
+        return self.mesh.num_triangles
+
+    def lower(self, lw) -> abi.Prim:
+        p = abi.Prim()
+        p.kind = abi.PRIM_MESH_INSTANCE
+        p.sdf_first, p.sdf_count = lw.mesh_range(self.mesh)
+        p.trs[:] = [float(v) for v in self.transform.trs()]
+        return p
+
+    def baked(self) -> Mesh:
+        """The same geometry as a plain Mesh with the transform baked into its vertices."""
+        m = self.mesh.transformed(self.transform)
+        m.material = self.material
+        return m
 
 
 def _load_json(src):
@@ -228,10 +266,12 @@ def _material_from_asset(d):
     return LambertianMaterial(alb)
 
 
-def load_scene_asset(src, aspect_ratio: float, base_dir=None):
+def load_scene_asset(src, aspect_ratio: float, base_dir=None, instances: bool = False):
     """SceneAsset JSON (asset.rs:103-146) -> (objects, lights, camera).  Entity meshes/materials
     are asset paths (resolved against the scene file's directory) or inline asset dicts; the
-    entity transform is baked into the mesh vertices.  Light types: point, directional, spot,
+    entity transform is baked into the mesh vertices, or with instances=True every entity becomes a
+    MeshInstance carrying its transform, and entities that name the same mesh share one Mesh (one
+    vertex range, one BVH).  Light types: point, directional, spot,
     ambient (light.rs).  SceneCamera.fov is in radians (Camera::new_perspective)."""
     from .renderer import (AmbientLight, Camera, DirectionalLight, LambertianMaterial, PointLight,
                            SpotLight)
@@ -245,7 +285,7 @@ def load_scene_asset(src, aspect_ratio: float, base_dir=None):
     def tr(t):
         return Transform(position=tuple(t["position"]), rotation=tuple(t["rotation"]), scale=tuple(t["scale"]))
 
-    objects, mat_cache = [], {}
+    objects, mat_cache, mesh_cache = [], {}, {}
     for ent in d.get("entities", []):
         if not ent.get("mesh"):
             continue
@@ -253,7 +293,13 @@ def load_scene_asset(src, aspect_ratio: float, base_dir=None):
         if mkey not in mat_cache:
             mat_cache[mkey] = (_material_from_asset(_load_json(res(ent["material"]))) if ent.get("material")
                                else LambertianMaterial(Color(0.8, 0.8, 0.8, 1.0)))
-        mesh = Mesh.from_asset(res(ent["mesh"]), mat_cache[mkey]).transformed(tr(ent["transform"]))
+        if instances:
+            gkey = json.dumps(ent["mesh"], sort_keys=True) if isinstance(ent["mesh"], dict) else str(ent["mesh"])
+            if gkey not in mesh_cache:
+                mesh_cache[gkey] = Mesh.from_asset(res(ent["mesh"]))
+            mesh = MeshInstance(mesh_cache[gkey], tr(ent["transform"]), mat_cache[mkey])
+        else:
+            mesh = Mesh.from_asset(res(ent["mesh"]), mat_cache[mkey]).transformed(tr(ent["transform"]))
         mesh.name = ent.get("name", mesh.name)
         objects.append(mesh)
     lights = []

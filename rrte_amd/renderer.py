@@ -770,6 +770,15 @@ class _Lowering:
         self.mesh_idx: list = []      # per mesh: (M, 3) uint32, offset into the shared vertex pool
         self._nverts = 0
         self._ntris = 0
+        self._mesh_range: dict = {}   # id(Mesh) -> its (first triangle, triangle count)
+
+    def mesh_range(self, mesh):
+        """The range of a Mesh object: added to the pools the first time the mesh or one of its
+        instances is lowered, shared afterwards (one Mesh object, one range)."""
+        k = id(mesh)
+        if k not in self._mesh_range:
+            self._mesh_range[k] = self.add_mesh(mesh.positions, mesh.normals, mesh.indices)
+        return self._mesh_range[k]
 
     def add_mesh(self, pos, nrm, idx):
         """Append a mesh to the shared pools; returns (first triangle, triangle count)."""
@@ -851,6 +860,13 @@ class Context:
         s = abi.Stats()
         self.check(self.lib.rrte_hip_stats(self.h, C.byref(s)))
         return s
+
+    def mesh_info(self) -> abi.MeshInfo:
+        """rrte_hip_mesh_info (include/rrte_hip_mesh.h): BVH builds so far, and the distinct triangle
+        ranges, triangle slots and BVH records of the scene the context holds."""
+        m = abi.MeshInfo()
+        self.check(self.lib.rrte_hip_mesh_info(self.h, C.byref(m)))
+        return m
 
     def close(self):
         if self.h:
@@ -991,15 +1007,15 @@ class Raytracer:
     @staticmethod
     def hit_objects(objects, hits) -> list:
         """The Python object behind each hit record: None for a miss, the object, or for a Mesh the
-        pair (mesh, triangle index in the mesh's own index order)."""
-        from .mesh import Mesh
+        pair (mesh, triangle index in the mesh's own index order); likewise for a MeshInstance."""
+        from .mesh import Mesh, MeshInstance
         out = []
         for prim, tri in zip(np.asarray(hits["prim"]).reshape(-1), np.asarray(hits["tri"]).reshape(-1)):
             if prim < 0:
                 out.append(None)
             else:
                 o = objects[int(prim)]
-                out.append((o, int(tri)) if isinstance(o, Mesh) else o)
+                out.append((o, int(tri)) if isinstance(o, (Mesh, MeshInstance)) else o)
         return out
 
     def stats(self) -> abi.Stats:

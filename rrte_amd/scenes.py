@@ -227,6 +227,59 @@ def mesh_demo(width=1920, height=1080, mode="lambert_shadow", detail=1.0):
     return objects, _showcase_lights(), cam, _config(width, height, Color(0.05, 0.05, 0.08, 1.0), mode)
 
 
+# Unit quaternions (x, y, z, w) of instance_demo, as decimal literals so that every mirror of the scene
+# lowers the same f32 values: 90 deg about Y, 45 deg about X, 45 deg about Y, and 45 deg about X then Y.
+Q_Y90 = (0.0, 0.70710677, 0.0, 0.70710677)
+Q_X45 = (0.38268343, 0.0, 0.0, 0.9238795)
+Q_Y45 = (0.0, 0.38268343, 0.0, 0.9238795)
+Q_X45_Y45 = (0.35355338, 0.35355338, -0.14644662, 0.8535534)
+
+# (base, position, rotation, scale) of instance_demo's instances: each base under a rigid, a uniformly
+# scaled, a non-uniformly scaled and a mirrored transform.
+INSTANCE_DEMO_PLACEMENTS = [
+    ("ball", (-3.0, 0.0, 1.5), Q_Y90, (1.0, 1.0, 1.0)),
+    ("ball", (2.5, 0.0, 2.5), (0.0, 0.0, 0.0, 1.0), (0.5, 0.5, 0.5)),
+    ("ball", (-2.5, 0.2, -2.5), Q_Y45, (1.6, 0.6, 1.0)),
+    ("ball", (3.5, 0.5, -1.0), Q_X45, (-1.0, 1.0, 1.0)),
+    ("ring", (0.0, 2.6, -1.5), Q_X45, (1.0, 1.0, 1.0)),
+    ("ring", (0.0, 0.4, 0.0), (0.0, 0.0, 0.0, 1.0), (1.5, 1.5, 1.5)),
+    ("ring", (-4.5, 1.5, 0.0), Q_X45_Y45, (0.5, 1.5, 0.8)),
+    ("ring", (4.5, 1.2, 1.5), Q_Y45, (1.0, -0.7, 1.0)),
+]
+
+
+def instance_demo_meshes(detail=1.0):
+    """The two base meshes of instance_demo: an icosphere standing on the ground and a torus about
+    the origin.  `detail` scales the triangle counts (1.0: 1280 + 2304 triangles; <= 0.25: 320 + 256)."""
+    from .mesh import icosphere, torus
+    sub = 3 if detail >= 1.0 else 2
+    nu = max(16, int(48 * detail ** 0.5)) if detail > 0.25 else 16
+    ball = icosphere((0.0, 1.0, 0.0), 1.0, sub, LambertianMaterial(Color.rgb(0.8, 0.35, 0.3)))
+    ring = torus((0.0, 0.0, 0.0), 1.0, 0.3, nu, nu // 2, LambertianMaterial(Color.rgb(0.3, 0.5, 0.85)))
+    return ball, ring
+
+
+def instance_demo(width=1920, height=1080, mode="lambert_shadow", detail=1.0, meshes=None):
+    """Mesh instances (RRTE_PRIM_MESH_INSTANCE): the ground sphere, the base icosphere as a plain mesh,
+    and eight instances of it and of a base torus (INSTANCE_DEMO_PLACEMENTS), every instance of a
+    base sharing the base's one vertex range and BVH.  Two point lights."""
+    from .math import Transform
+    from .mesh import MeshInstance
+    ball, ring = meshes if meshes is not None else instance_demo_meshes(detail)
+    base = {"ball": ball, "ring": ring}
+    tints = [Color.rgb(0.85, 0.8, 0.4), Color.rgb(0.4, 0.8, 0.5)]
+    mats = [LambertianMaterial(c) for c in tints]
+    objects = [Sphere((0.0, -1000.0, 0.0), 1000.0, LambertianMaterial(Color.rgb(0.2, 0.2, 0.2))), ball]
+    for k, (which, pos, rot, scale) in enumerate(INSTANCE_DEMO_PLACEMENTS):
+        # every other instance keeps its base's material (the default), the rest get a tint
+        objects.append(MeshInstance(base[which], Transform(position=pos, rotation=rot, scale=scale),
+                                    mats[(k // 2) % 2] if k % 2 else None))
+    lights = [PointLight((-10.0, 15.0, 10.0), Color.rgb(1.0, 1.0, 1.0), 25.0),
+              PointLight((10.0, 10.0, 15.0), Color.rgb(0.6, 0.7, 1.0), 15.0)]
+    cam = _camera(width, height, (0.0, 6.0, 12.0), (0.0, 1.0, 0.0), 45.0)
+    return objects, lights, cam, _config(width, height, Color(0.05, 0.05, 0.08, 1.0), mode)
+
+
 SCENES = {
     "basic-demo": basic_demo,
     "simple-demo": simple_demo,
@@ -236,6 +289,8 @@ SCENES = {
     "deformation-stress": deformation_stress,
     "mesh-demo": mesh_demo,
 }
+# (instance_demo is not a BASELINE scene: the CPU oracle has no mesh-instance object; its checker is
+# tests/instance_ref.py)
 
 
 def animate_values(sc, f):

@@ -164,3 +164,5 @@ extern "C" {
 pub mod safe;
 // ray queries (include/rrte_hip_query.h): their own extern block, records and safe wrappers
 pub mod query;
+// mesh instances and mesh sharing diagnostics (include/rrte_hip_mesh.h): likewise
+pub mod mesh;
