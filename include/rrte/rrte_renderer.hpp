@@ -23,6 +23,7 @@
 
 #include "../rrte_hip.h"
 #include "../rrte_hip_query.h"
+#include "../rrte_hip_refit.h"
 
 namespace rrte_math {
 
@@ -268,8 +269,15 @@ public:
     Mesh(std::vector<float> positions, std::vector<uint32_t> indices, std::vector<float> normals = {},
          std::shared_ptr<Material> m = nullptr);
     rrte_prim lower(Lowering&) const override;
+    // Deform the mesh: new positions for the same vertices (the indices stay) and new normals,
+    // recomputed from the faces as the constructor does when empty.  Render with
+    // Raytracer::render_deformed afterwards to refit the BVH instead of rebuilding it.  Throws
+    // (RRTE_INVALID_ARG) when the vertex count differs.
+    void set_vertices(std::vector<float> new_positions, std::vector<float> new_normals = {});
     std::vector<float> positions, normals;
     std::vector<uint32_t> indices;
+private:
+    void unit_normals(std::vector<float> nrm);
 };
 
 // A Mesh placed in the world through a transform (RRTE_PRIM_MESH_INSTANCE, include/rrte_hip.h): the
@@ -391,6 +399,14 @@ public:
     // (the reference passes it through unused); objects carry their materials.
     std::vector<uint8_t> render(const Objects& objects, const Lights& lights, const Materials& materials,
                                 const Camera& camera);
+    // render() for a scene whose meshes are a deformation of the last rendered ones (same topology:
+    // Mesh::set_vertices): lowers once, announces the new vertices with rrte_hip_mesh_refit
+    // (include/rrte_hip_refit.h) and renders that same lowered scene, so the BVHs are refitted on the
+    // device instead of rebuilt on the host.  Bit-identical to render().  A refit the library refuses
+    // (nothing built yet, another topology, a non-finite vertex) falls back to the plain build.
+    std::vector<uint8_t> render_deformed(const Objects& objects, const Lights& lights, const Materials& materials,
+                                         const Camera& camera);
+    rrte_refit_info refit_info() const;
     // Engine::render_frame's loop (engine.rs:82,293; rust/patches/0002): the frame into the caller's
     // buffer, reused every frame and pinned once (rrte_hip_host_register) so the kernel stores the
     // frame straight into it.  `out` is resized to W*H*4; a buffer that moved since it was pinned is

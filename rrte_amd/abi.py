@@ -197,6 +197,22 @@ MESH_EXPORTS = {
     "rrte_hip_mesh_info": (C.c_int, [_P, C.POINTER(MeshInfo)]),
 }
 
+# ------------------------------------------------ deforming meshes (include/rrte_hip_refit.h)
+class RefitInfo(C.Structure):
+    _fields_ = [("refits", C.c_uint64), ("device_refits", C.c_uint64), ("levels", C.c_uint32),
+                ("deformed", C.c_uint32)]
+
+
+assert C.sizeof(RefitInfo) == 24
+
+# Every entry point include/rrte_hip_refit.h declares.
+REFIT_EXPORTS = {
+    "rrte_hip_mesh_refit": (C.c_int, [_P, C.POINTER(SceneIR)]),
+    "rrte_hip_refit_info": (C.c_int, [_P, C.POINTER(RefitInfo)]),
+    "rrte_hip_mesh_nodes": (C.c_int, [_P, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "rrte_hip_mesh_slots": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]),
+}
+
 _lib = None
 
 
@@ -217,7 +233,7 @@ def load() -> C.CDLL:
     except Exception:
         pass
     lib = C.CDLL(str(LIB_PATH), mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**EXPORTS, **QUERY_EXPORTS, **MESH_EXPORTS}.items():
+    for name, (res, args) in {**EXPORTS, **QUERY_EXPORTS, **MESH_EXPORTS, **REFIT_EXPORTS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

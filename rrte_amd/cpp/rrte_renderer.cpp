@@ -272,10 +272,21 @@ rrte_prim Capsule::lower(Lowering&) const {
 Mesh::Mesh(std::vector<float> pos, std::vector<uint32_t> idx, std::vector<float> nrm, std::shared_ptr<Material> m)
     : positions(std::move(pos)), indices(std::move(idx)) {
     material_ = std::move(m);
-    const size_t nv = positions.size() / 3, nt = indices.size() / 3;
+    const size_t nv = positions.size() / 3;
     if (positions.size() % 3 || indices.size() % 3) throw Error(RRTE_INVALID_ARG, "mesh arrays must hold triples");
     for (uint32_t i : indices)
         if (i >= nv) throw Error(RRTE_INVALID_ARG, "mesh index out of range");
+    unit_normals(std::move(nrm));
+}
+void Mesh::set_vertices(std::vector<float> new_positions, std::vector<float> new_normals) {
+    if (new_positions.size() != positions.size()) throw Error(RRTE_INVALID_ARG, "set_vertices: the vertex count differs");
+    if (!new_normals.empty() && new_normals.size() != positions.size())
+        throw Error(RRTE_INVALID_ARG, "set_vertices: normals must match the vertices");
+    positions = std::move(new_positions);
+    unit_normals(std::move(new_normals));
+}
+void Mesh::unit_normals(std::vector<float> nrm) {
+    const size_t nv = positions.size() / 3, nt = indices.size() / 3;
     auto P = [&](uint32_t i) { return Vec3(positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]); };
     if (nrm.empty()) {  // face normals summed per vertex (rrte_amd/mesh.py: k-major, face order)
         nrm.assign(3 * nv, 0.0f);
@@ -632,6 +643,22 @@ std::vector<uint8_t> Raytracer::render(const Objects& objects, const Lights& lig
     std::vector<uint8_t> out((size_t)p.width * p.height * 4);
     check(rrte_hip_render(ctx_, &sc.ir(), &p, out.data()));
     return out;
+}
+std::vector<uint8_t> Raytracer::render_deformed(const Objects& objects, const Lights& lights,
+                                                const Materials& materials, const Camera& camera) {
+    (void)materials;
+    const LoweredScene sc(objects, lights, camera);
+    const rrte_status rs = rrte_hip_mesh_refit(ctx_, &sc.ir());
+    if (rs != RRTE_OK && rs != RRTE_INVALID_ARG) check(rs);  // (INVALID_ARG: refused; the render below builds)
+    const rrte_render_params p = config_.lower();
+    std::vector<uint8_t> out((size_t)p.width * p.height * 4);
+    check(rrte_hip_render(ctx_, &sc.ir(), &p, out.data()));
+    return out;
+}
+rrte_refit_info Raytracer::refit_info() const {
+    rrte_refit_info r;
+    check(rrte_hip_refit_info(ctx_, &r));
+    return r;
 }
 void Raytracer::render_into(const Objects& objects, const Lights& lights, const Materials& materials,
                             const Camera& camera, std::vector<uint8_t>& out) {

@@ -9,6 +9,7 @@
 // the triangle -- always lies inside every box on its path, and ties broken by the original index.  Triangles are stored in leaf order with
 // e1 = v1 - v0 and e2 = v2 - v0 precomputed (the same f32 subtractions the test performs).
 #include "bvh.hpp"
+#include "mesh_box.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -19,28 +20,6 @@ namespace {
 
 constexpr int kBins = 16;
 constexpr uint32_t kLeafMax = 4;
-
-struct Box {
-    float lo[3] = {INFINITY, INFINITY, INFINITY};
-    float hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    void grow(const float* p) {
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = std::min(lo[k], p[k]);
-            hi[k] = std::max(hi[k], p[k]);
-        }
-    }
-    void grow(const Box& b) {
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = std::min(lo[k], b.lo[k]);
-            hi[k] = std::max(hi[k], b.hi[k]);
-        }
-    }
-    float area() const {
-        float d[3];
-        for (int k = 0; k < 3; ++k) d[k] = std::max(0.0f, hi[k] - lo[k]);
-        return 2.0f * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]);
-    }
-};
 
 struct BTri {
     Box box;
@@ -63,21 +42,6 @@ struct Builder {
     bool too_deep = false;
 
     explicit Builder(std::vector<BTri>& tris) : t(tris) {}
-
-    // Inflation: 1 % of the leaf's extent plus a relative term on its coordinates.
-    static Box inflate(Box b) {
-        float ext = 0.0f, mag = 0.0f;
-        for (int k = 0; k < 3; ++k) {
-            ext = std::max(ext, b.hi[k] - b.lo[k]);
-            mag = std::max(mag, std::max(std::fabs(b.lo[k]), std::fabs(b.hi[k])));
-        }
-        const float d = 1e-2f * ext + 1e-5f * mag + 1e-6f;
-        for (int k = 0; k < 3; ++k) {
-            b.lo[k] = std::nextafter(b.lo[k] - d, -INFINITY);
-            b.hi[k] = std::nextafter(b.hi[k] + d, INFINITY);
-        }
-        return b;
-    }
 
     // Builds the subtree over t[b, e); returns its link and (inflated) box.
     std::pair<uint32_t, Box> build(uint32_t b, uint32_t e, uint32_t depth) {

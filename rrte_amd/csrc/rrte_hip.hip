@@ -30,7 +30,9 @@
 #include <vector>
 
 #include "../../include/rrte_hip_mesh.h"
+#include "../../include/rrte_hip_refit.h"
 #include "bvh.hpp"
+#include "mesh_refit.hpp"
 #include "jit.hpp"
 #include "sdf_guard.hpp"
 #include "ray_kernels.hpp"
@@ -237,6 +239,17 @@ struct rrte_ctx {
     std::vector<unsigned char> mesh_cache_key;  // MeshKey, then the arrays' content when mesh_version is 0
     bool mesh_cache_valid = false;
     uint64_t bvh_builds = 0;  // distinct ranges built since the context was created (rrte_hip_mesh_info)
+    // Deforming meshes (include/rrte_hip_refit.h).  mesh_cache_indices: the indices the
+    // cache was built from (rrte_hip_mesh_refit compares the caller's against them).  While
+    // mesh_deformed is set the cache's key names arrays whose vertices differ from the ones mesh_cache's
+    // records were built from: every scene version made from it is refitted on the device from the
+    // scene's vertices (upload_scene) and mesh_cache itself is never uploaded unrefitted; only its
+    // ranges' lo / hi (the culling spheres) follow the vertices on the host.  A real build clears it.
+    std::vector<uint32_t> mesh_cache_indices;
+    bool mesh_deformed = false;
+    RefitStatic refit_static;         // of mesh_cache's topology (first refit after a build)
+    bool refit_static_valid = false;
+    uint64_t refits = 0, device_refits = 0;
     bool env_generic_all = false;    // RRTE_GENERIC_ALL=1: the all-features generic kernel for every scene (A/B, tests)
     // Batched gathers render the batch's frames in multi-frame launches at its close (default), or with
     // RRTE_BATCH_LAUNCH=0 each frame at its call (its own launch on the caller's stream: the root in
@@ -885,6 +898,13 @@ bool mesh_cache_hit(const rrte_ctx* c, const SceneKeyParts& kp, const rrte_scene
     return want == have;
 }
 
+void set_mesh_cache_key(rrte_ctx* c, const SceneKeyParts& kp) {
+    c->mesh_cache_key.clear();
+    for (int i = 4; i < 7; ++i)
+        c->mesh_cache_key.insert(c->mesh_cache_key.end(), static_cast<const unsigned char*>(kp.parts[i]),
+                                 static_cast<const unsigned char*>(kp.parts[i]) + kp.lens[i]);
+}
+
 rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, double* upload_ms) {
     const size_t bn = sizeof(rrte_sdf_node) * s->num_sdf_nodes;
     SceneKeyParts kparts;
@@ -931,13 +951,17 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
         if (built.too_deep) return fail(c, RRTE_UNSUPPORTED_PRIM, "mesh BVH deeper than the traversal stack");
         c->bvh_builds += built.ranges.size();
         c->mesh_cache = std::move(built);
-        c->mesh_cache_key.clear();
-        for (int i = 4; i < 7; ++i)
-            c->mesh_cache_key.insert(c->mesh_cache_key.end(), static_cast<const unsigned char*>(kparts.parts[i]),
-                                     static_cast<const unsigned char*>(kparts.parts[i]) + kparts.lens[i]);
+        set_mesh_cache_key(c, kparts);
+        c->mesh_cache_indices.assign(s->mesh_indices, s->mesh_indices + s->num_mesh_indices);
         c->mesh_cache_valid = true;
+        c->mesh_deformed = false;  // (a real build: the records are these vertices')
+        c->refit_static_valid = false;
     }
     const MeshData& md = c->mesh_cache;
+    // A deformed cache (rrte_hip_mesh_refit): md's records are stale; this version is refitted on the
+    // device from the scene's vertices, behind the copy (below)
+    const bool refit = c->mesh_deformed && c->refit_static_valid && !md.tris.empty();
+    const RefitStatic& rs = c->refit_static;
     assign_mesh_prims(s, md, prims.data(), bounds.data());
     lap_up(1);
     // SDF programs with their exact CSG early-outs (sdf_guard.hpp); the key above stays the caller's IR
@@ -962,7 +986,8 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
     c->scene_key.clear();
     // one allocation, one staging buffer, one copy (256-B aligned sub-arrays)
     struct Part { const void* src; size_t bytes; size_t off; };
-    Part parts[9] = {{prims.data(), prims.size() * sizeof(DPrim), 0},
+    constexpr int kParts = 13;  // 9-12: the refit's inputs (empty unless this version is refitted)
+    Part parts[kParts] = {{prims.data(), prims.size() * sizeof(DPrim), 0},
                      {mats.data(), mats.size() * sizeof(DMaterial), 0},
                      {lights.data(), lights.size() * sizeof(DLight), 0},
                      {nodes.data(), bn, 0},
@@ -970,7 +995,11 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
                      {md.nodes.data(), md.nodes.size() * sizeof(float4), 0},
                      {md.tris.data(), md.tris.size() * sizeof(float4), 0},
                      {md.norms.data(), md.norms.size() * sizeof(float4), 0},
-                     {md.perm.data(), md.perm.size() * sizeof(uint32_t), 0}};
+                     {md.perm.data(), md.perm.size() * sizeof(uint32_t), 0},
+                     {s->mesh_vertices, refit ? s->num_mesh_vertices * sizeof(rrte_mesh_vertex) : 0, 0},
+                     {rs.slot_vtx.data(), refit ? rs.slot_vtx.size() * sizeof(uint32_t) : 0, 0},
+                     {rs.leaves.data(), refit ? rs.leaves.size() * sizeof(uint2) : 0, 0},
+                     {rs.order.data(), refit ? rs.order.size() * sizeof(uint2) : 0, 0}};
     lap_up(4);
     size_t total = 0;
     for (Part& pt : parts) {
@@ -1005,6 +1034,22 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
                            reinterpret_cast<const rrte_sdf_node*>(B.d_buf + parts[3].off), (uint32_t)nodes.size(),
                            c->d_counters);
         HIPCHK(c, hipGetLastError());
+    }
+    if (refit) {  // on the upload stream: launches wait for ev_up, frames in flight read other versions
+        RefitDevice rd{};
+        rd.nodes = reinterpret_cast<float4*>(B.d_buf + parts[5].off);
+        rd.tris = reinterpret_cast<float4*>(B.d_buf + parts[6].off);
+        rd.norms = reinterpret_cast<float4*>(B.d_buf + parts[7].off);
+        rd.verts = reinterpret_cast<const float2*>(B.d_buf + parts[9].off);
+        rd.slot_vtx = reinterpret_cast<const uint32_t*>(B.d_buf + parts[10].off);
+        rd.leaves = reinterpret_cast<const uint2*>(B.d_buf + parts[11].off);
+        rd.order = reinterpret_cast<const uint2*>(B.d_buf + parts[12].off);
+        rd.n_verts = s->num_mesh_vertices;
+        rd.n_slots = (uint32_t)(md.tris.size() / 3);
+        rd.n_recs = (uint32_t)(md.nodes.size() / 4);
+        rd.check = (c->env_debug & 4u) ? c->d_counters + 1 : nullptr;
+        HIPCHK(c, launch_refit(rs, rd, us));
+        ++c->device_refits;
     }
     HIPCHK(c, hipEventRecord(B.ev_up, us));
     lap_up(7);
@@ -2395,6 +2440,84 @@ rrte_status rrte_hip_mesh_info(rrte_ctx* c, rrte_mesh_info* out) {
         out->tri_slots = (uint32_t)(c->mesh_cache.tris.size() / 3);
         out->bvh_nodes = (uint32_t)(c->mesh_cache.nodes.size() / 4);
     }
+    return RRTE_OK;
+}
+
+// include/rrte_hip_refit.h
+rrte_status rrte_hip_mesh_refit(rrte_ctx* c, const rrte_scene_ir* s) {
+    if (!c || !s) return RRTE_INVALID_ARG;
+    if ((s->num_mesh_vertices && !s->mesh_vertices) || (s->num_mesh_indices && !s->mesh_indices))
+        return fail(c, RRTE_INVALID_ARG, "mesh refit: null mesh array");
+    if (!c->mesh_cache_valid || c->mesh_cache_key.size() < sizeof(MeshKey))
+        return fail(c, RRTE_INVALID_ARG, "mesh refit: no mesh data to refit (nothing built yet)");
+    MeshKey have;
+    memcpy(&have, c->mesh_cache_key.data(), sizeof have);
+    if (have.nv != s->num_mesh_vertices)
+        return fail(c, RRTE_INVALID_ARG, "mesh refit: vertex count %u differs from the built %u", s->num_mesh_vertices, (uint32_t)have.nv);
+    if (have.ni != s->num_mesh_indices || c->mesh_cache_indices.size() != s->num_mesh_indices)
+        return fail(c, RRTE_INVALID_ARG, "mesh refit: index count %u differs from the built %u", s->num_mesh_indices, (uint32_t)have.ni);
+    if (s->num_mesh_indices && memcmp(c->mesh_cache_indices.data(), s->mesh_indices, sizeof(uint32_t) * s->num_mesh_indices))
+        return fail(c, RRTE_INVALID_ARG, "mesh refit: an index value differs from the built indices (topology change)");
+    {
+        std::vector<std::pair<uint32_t, uint32_t>> want = mesh_ranges_of(s), got;
+        for (const MeshRange& m : c->mesh_cache.ranges) got.emplace_back(m.first, m.count);
+        std::sort(want.begin(), want.end());
+        std::sort(got.begin(), got.end());
+        if (want != got) return fail(c, RRTE_INVALID_ARG, "mesh refit: the scene's triangle ranges differ from the built ones");
+    }
+    for (uint32_t v = 0; v < s->num_mesh_vertices; ++v) {
+        const float* p = s->mesh_vertices[v].position;
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]))
+            return fail(c, RRTE_INVALID_ARG, "mesh refit: vertex %u has a non-finite position", v);
+    }
+    if (!c->refit_static_valid) {  // first refit of this topology
+        RefitStatic rs;
+        if (!build_refit_static(c->mesh_cache, c->mesh_cache_indices.data(), (uint32_t)c->mesh_cache_indices.size(), rs))
+            return fail(c, RRTE_INVALID_ARG, "mesh refit: the stored mesh data does not describe trees over its triangles");
+        c->refit_static = std::move(rs);
+        c->refit_static_valid = true;
+    }
+    refit_range_bounds(s, c->mesh_cache);
+    SceneKeyParts kp;
+    scene_key_parts(s, kp);
+    set_mesh_cache_key(c, kp);
+    c->mesh_deformed = true;
+    ++c->refits;
+    return RRTE_OK;
+}
+
+rrte_status rrte_hip_refit_info(rrte_ctx* c, rrte_refit_info* out) {
+    if (!c || !out) return RRTE_INVALID_ARG;
+    memset(out, 0, sizeof *out);
+    out->refits = c->refits;
+    out->device_refits = c->device_refits;
+    out->levels = c->refit_static_valid ? c->refit_static.levels() : 0u;
+    out->deformed = (c->mesh_cache_valid && c->mesh_deformed) ? 1u : 0u;
+    return RRTE_OK;
+}
+
+rrte_status rrte_hip_mesh_nodes(rrte_ctx* c, void* out, size_t bytes, uint32_t* records) {
+    if (!c || !records || (bytes && !out)) return RRTE_INVALID_ARG;
+    *records = 0;
+    if (c->sb_cur < 0 || !c->mesh_cache_valid) return RRTE_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const rrte_ctx::SceneBuf& B = c->sb[c->sb_cur];
+    const size_t all = c->mesh_cache.nodes.size() * sizeof(float4);
+    *records = (uint32_t)(c->mesh_cache.nodes.size() / 4);
+    const size_t n = std::min(bytes, all);
+    if (!n) return RRTE_OK;
+    if (B.ev_up) HIPCHK(c, hipEventSynchronize(B.ev_up));
+    HIPCHK(c, hipMemcpy(out, c->mesh_view.nodes, n, hipMemcpyDeviceToHost));
+    return RRTE_OK;
+}
+
+rrte_status rrte_hip_mesh_slots(rrte_ctx* c, uint32_t* out, size_t count, uint32_t* slots) {
+    if (!c || !slots || (count && !out)) return RRTE_INVALID_ARG;
+    *slots = 0;
+    if (c->sb_cur < 0 || !c->mesh_cache_valid) return RRTE_OK;
+    const size_t all = c->mesh_cache.tris.size() / 3;
+    *slots = (uint32_t)all;
+    for (size_t k = 0; k < std::min(count, all); ++k) memcpy(out + k, &c->mesh_cache.tris[3 * k].w, sizeof(uint32_t));
     return RRTE_OK;
 }
 

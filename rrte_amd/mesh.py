@@ -70,16 +70,38 @@ class Mesh:
         self.indices = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
         if self.indices.size and int(self.indices.max()) >= len(self.positions):
             raise ValueError("mesh index out of range")
+        self.normals = self._unit_normals(normals)
+        self.material = material
+        self.transform = Transform.identity()  # ignored, like Triangle's (bake transforms into vertices)
+        self.name = name
+
+    def _unit_normals(self, normals) -> np.ndarray:
         if normals is None:  # area-weighted vertex normals from the faces, then normalised
             acc = np.zeros_like(self.positions)
             fn = face_normals(self.positions, self.indices)
             for k in range(3):
                 np.add.at(acc, self.indices[:, k], fn)
             normals = acc
-        self.normals = normalize_rows(np.asarray(normals, dtype=F).reshape(-1, 3))
-        self.material = material
-        self.transform = Transform.identity()  # ignored, like Triangle's (bake transforms into vertices)
-        self.name = name
+        return normalize_rows(np.asarray(normals, dtype=F).reshape(-1, 3))
+
+    def set_vertices(self, positions, normals=None):
+        """Deform the mesh: new float32 positions for the same vertices (the indices stay), and new
+        normals, recomputed from the faces as the constructor does when omitted.  Render the scene
+        with Raytracer.render_deformed afterwards to refit the BVH instead of rebuilding it.
+        ValueError when the vertex count or a shape differs."""
+        pos = np.asarray(positions)
+        if pos.dtype.kind not in "fiu":
+            raise ValueError(f"positions must be numeric, not {pos.dtype}")
+        if pos.ndim != 2 or pos.shape != self.positions.shape:
+            raise ValueError(f"positions must have shape {self.positions.shape}, not {pos.shape}")
+        if normals is not None:
+            nrm = np.asarray(normals)
+            if nrm.dtype.kind not in "fiu":
+                raise ValueError(f"normals must be numeric, not {nrm.dtype}")
+            if nrm.shape != self.positions.shape:
+                raise ValueError(f"normals must have shape {self.positions.shape}, not {nrm.shape}")
+        self.positions = np.array(pos, dtype=F, order="C")  # (a copy: the caller's array may change)
+        self.normals = self._unit_normals(normals)
 
     # ---- SceneObject surface
     def set_material(self, material):

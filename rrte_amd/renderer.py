@@ -868,6 +868,41 @@ class Context:
         self.check(self.lib.rrte_hip_mesh_info(self.h, C.byref(m)))
         return m
 
+    def mesh_refit(self, lowered: "LoweredScene") -> None:
+        """rrte_hip_mesh_refit (include/rrte_hip_refit.h): the mesh arrays of `lowered` are a
+        deformation (same counts, same indices) of the ones the context's mesh data was built or last
+        refitted from; its next render or query refits the BVHs on the device instead of building.
+        Host only.  Raises RrteError (INVALID_ARG) when the refit is refused; the context is then
+        as it was."""
+        self.check(self.lib.rrte_hip_mesh_refit(self.h, lowered.ref()))
+
+    def refit_info(self) -> abi.RefitInfo:
+        """rrte_hip_refit_info: accepted refits, scene versions refitted on the device, propagate
+        launches per refit, and whether the mesh cache is in the deformed state."""
+        r = abi.RefitInfo()
+        self.check(self.lib.rrte_hip_refit_info(self.h, C.byref(r)))
+        return r
+
+    def mesh_nodes(self) -> np.ndarray:
+        """rrte_hip_mesh_nodes: the current scene version's BVH interior records as a (records, 4, 4)
+        float32 array (child 0 lo + link, hi + axis, child 1 lo + link, hi); view it as uint32 for
+        the links.  Waits for that version's upload."""
+        n = C.c_uint32()
+        self.check(self.lib.rrte_hip_mesh_nodes(self.h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 4, 4), dtype=np.float32)
+        if n.value:
+            self.check(self.lib.rrte_hip_mesh_nodes(self.h, out.ctypes.data, out.nbytes, C.byref(n)))
+        return out
+
+    def mesh_slots(self) -> np.ndarray:
+        """rrte_hip_mesh_slots: per device triangle slot, the index of its triangle within its range."""
+        n = C.c_uint32()
+        self.check(self.lib.rrte_hip_mesh_slots(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            self.check(self.lib.rrte_hip_mesh_slots(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)))
+        return out
+
     def close(self):
         if self.h:
             self.lib.rrte_hip_destroy(self.h)
@@ -937,8 +972,30 @@ class Raytracer:
 
     def render_f32(self, objects, lights, materials, camera: Camera, want_f32=True, linear=False):
         """Parity variant: also returns the post-gamma/clamp (or linear) f32 RGBA buffer."""
+        return self._render_f32(objects, lights, camera, want_f32, linear, deformed=False)
+
+    def render_deformed(self, objects, lights, materials, camera: Camera) -> np.ndarray:
+        """render() for a scene whose meshes are a deformation of the last rendered ones (same
+        topology: Mesh.set_vertices): lowers once, announces the new vertices with
+        rrte_hip_mesh_refit and renders that same lowered scene, so the BVHs are refitted on the device
+        instead of rebuilt on the host.  Bit-identical to render().  A refit the
+        library refuses (nothing built yet, another topology, other ranges, a non-finite vertex) falls
+        back to the plain build."""
+        out, _ = self.render_f32_deformed(objects, lights, materials, camera, want_f32=False)
+        return out
+
+    def render_f32_deformed(self, objects, lights, materials, camera: Camera, want_f32=True, linear=False):
+        """render_f32() through the refit path (render_deformed)."""
+        return self._render_f32(objects, lights, camera, want_f32, linear, deformed=True)
+
+    def _render_f32(self, objects, lights, camera: Camera, want_f32, linear, deformed):
         cfg = self.config
         scene = LoweredScene(objects, lights, camera)
+        if deformed:
+            ctx = self.ctx
+            st = ctx.lib.rrte_hip_mesh_refit(ctx.h, scene.ref())
+            if st not in (abi.RRTE_OK, abi.RRTE_INVALID_ARG):  # (INVALID_ARG: refused; the render below builds)
+                ctx.check(st)
         prm = cfg.lower()
         if linear:
             prm.flags |= abi.FLAG_F32_LINEAR

@@ -166,3 +166,5 @@ pub mod safe;
 pub mod query;
 // mesh instances and mesh sharing diagnostics (include/rrte_hip_mesh.h): likewise
 pub mod mesh;
+// deforming meshes, device-side BVH refit (include/rrte_hip_refit.h): likewise
+pub mod refit;
