@@ -213,6 +213,16 @@ REFIT_EXPORTS = {
     "rrte_hip_mesh_slots": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]),
 }
 
+# ------------------------------------------------ specialised-kernel diagnostics (include/rrte_hip_jit.h)
+ENTRY_NONE, ENTRY_GENERIC, ENTRY_GENERAL, ENTRY_PLAIN = 0, 1, 2, 3
+
+# Every entry point include/rrte_hip_jit.h declares.
+JIT_EXPORTS = {
+    "rrte_hip_jit_entry": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "rrte_hip_tile_rects": (C.c_int, [C.POINTER(SceneIR), C.POINTER(RenderParams), C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+}
+
 _lib = None
 
 
@@ -233,7 +243,7 @@ def load() -> C.CDLL:
     except Exception:
         pass
     lib = C.CDLL(str(LIB_PATH), mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**EXPORTS, **QUERY_EXPORTS, **MESH_EXPORTS, **REFIT_EXPORTS}.items():
+    for name, (res, args) in {**EXPORTS, **QUERY_EXPORTS, **MESH_EXPORTS, **REFIT_EXPORTS, **JIT_EXPORTS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -13,6 +13,7 @@ namespace rrte {
 struct JitKernel {
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;
+    hipFunction_t fn_plain = nullptr;  // the plain-launch entry (jit.hip append_kernel), if the module has one
     double compile_ms = 0.0;
     size_t code_bytes = 0;
     bool from_cache = false;
@@ -29,7 +30,8 @@ struct JitTopo {
 
 // HIP source for one scene + shading mode and an extern "C" rrte_jit_kernel instantiating
 // ray_kernel_body<mode, Scene, single, cull> (single: one sample, one bounce -> straight-line code;
-// else runtime sample/bounce loops).  topo == nullptr: a FULL kernel, the whole scene as static
+// else runtime sample/bounce loops); a single FULL kernel's module also has rrte_jit_kernel_plain, the
+// same body under the LaunchPlain traits.  topo == nullptr: a FULL kernel, the whole scene as static
 // constexpr arrays.  Otherwise a TOPOLOGY kernel: only the structure is compiled in and the values
 // come from the uploaded records (kernel argument rrte::SceneValues); its source -- and so its code
 // object -- depends on the scene's topology only (jit_topology_key).

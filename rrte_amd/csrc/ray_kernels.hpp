@@ -2167,9 +2167,29 @@ __device__ __forceinline__ Col ray_color_ref(const S& sc, const KParams& kp, Ray
 // all 64 lanes of the wave (`live` marks the lanes that own a pixel): with
 // CULL the hit-point bound and the per-light shadow culls are wave reductions.
 constexpr bool kShadeAll = RRTE_MARCH_PRED >= 3;  // shade every lane (predicated), or only hit lanes
-template <class S, bool CULL>
+
+// Launch traits of ray_kernel_body: what the kernel may assume about its launch at compile time.
+// LaunchAny assumes nothing.  LaunchPlain is the frame an engine renders in a stream (the host checks
+// every condition before it picks that entry, rrte_hip.hip plain_launch): one frame per launch
+// (nframes 1, the output is the argument pointer), no band map (band_rows, row0, out_image_rows 0),
+// debug 0, no f32 output, RGBA8 stores to device memory (no slab, no host-store flag), gamma 2.2, one
+// sample per pixel (inv_spp 1).  Those launch values are then constants and the per-wave checks on
+// them (a scalar load, a wait and a branch each) fold away.  The tile list and the tile profile
+// (KParams::hot, tile_cost) stay run-time values: a stream's frames use the list, and a profiled
+// launch then times the entry the list is for.  The values are read
+// through accessors, never from a patched copy of KParams: a copy sends the 3.5 KB block to scratch.
+struct LaunchAny { static constexpr bool kPlain = false; };
+struct LaunchPlain { static constexpr bool kPlain = true; };
+template <class LT>
+__device__ __forceinline__ uint32_t launch_debug(const KParams& kp) {
+    if constexpr (LT::kPlain) return 0u;
+    else return kp.debug;
+}
+
+template <class S, bool CULL, class LT = LaunchAny>
 __device__ __forceinline__ Col shade_lambert(const S& sc, const KParams& kp, const Cull& cl, const Ray& r, bool live,
                                              uint32_t& nshadow, uint32_t pmask) {
+    const uint32_t debug = launch_debug<LT>(kp);
     Col out{0.0f, 0.0f, 0.0f, 1.0f};
     if (kp.max_depth == 0) return out;
     Hit h;
@@ -2179,11 +2199,11 @@ __device__ __forceinline__ Col shade_lambert(const S& sc, const KParams& kp, con
     h.front = true;
     h.sub = 0u;
     // RRTE_DEBUG bit 7 (timing diagnostics only, with bit 1): the closest-hit search without hit attributes
-    const int idx = closest_hit(sc, r, live ? kp.t_min : kInf, h, pmask, !(kp.debug & 128u));  // idle lanes find nothing
+    const int idx = closest_hit(sc, r, live ? kp.t_min : kInf, h, pmask, !(debug & 128u));  // idle lanes find nothing
     const DMaterial* m = idx >= 0 ? material_of(sc, idx) : nullptr;
     const bool hit = m != nullptr;
     if (idx < 0) out = Col{kp.bg[0], kp.bg[1], kp.bg[2], kp.bg[3]};
-    if (kp.debug & 2u) {  // diagnostics: primary visibility only
+    if (debug & 2u) {  // diagnostics: primary visibility only
         if (idx >= 0) out = Col{h.t * 0.01f, 0.0f, 0.0f, 1.0f};
         return out;
     }
@@ -2217,8 +2237,8 @@ __device__ __forceinline__ Col shade_lambert(const S& sc, const KParams& kp, con
         nshadow += cast ? 1u : 0u;
         {
             const Ray sr = ray_new_unit(vadd(h.p, vmuls(h.n, bias)), cast ? k.dir : V(0.0f, 1.0f, 0.0f));
-            const bool skip = (kp.debug & 1u) || ((kp.debug & 256u) && li != ((kp.debug >> 9) & 7u));
-            const bool occ = !skip && occluded(sc, sr, bias, cast ? k.dist : -kInf, smask, (kp.debug & 64u) ? idx : -1);
+            const bool skip = (debug & 1u) || ((debug & 256u) && li != ((debug >> 9) & 7u));
+            const bool occ = !skip && occluded(sc, sr, bias, cast ? k.dist : -kInf, smask, (debug & 64u) ? idx : -1);
             if (cast && !occ) {
                 float f = k.att * ndl;
                 cr = cr + ar * (k.cr * f);
@@ -2233,8 +2253,8 @@ __device__ __forceinline__ Col shade_lambert(const S& sc, const KParams& kp, con
             ++nshadow;
             Ray sr = ray_new_unit(vadd(h.p, vmuls(h.n, bias)), k.dir);
             // RRTE_DEBUG bit 6 (timing diagnostics only, wrong images): skip the object the ray starts on
-            if ((kp.debug & 1u) || ((kp.debug & 256u) && li != ((kp.debug >> 9) & 7u)) ||
-                !occluded(sc, sr, bias, k.dist, smask, (kp.debug & 64u) ? idx : -1)) {
+            if ((debug & 1u) || ((debug & 256u) && li != ((debug >> 9) & 7u)) ||
+                !occluded(sc, sr, bias, k.dist, smask, (debug & 64u) ? idx : -1)) {
                 float f = k.att * ndl;
                 cr = cr + ar * (k.cr * f);
                 cg = cg + ag * (k.cg * f);
@@ -2297,17 +2317,35 @@ __device__ __forceinline__ float rclamp(float x) {
 // (rrte_hip_fpcheck RRTE_FPCHECK_GAMMA_U8, tests/test_gpu_fpexact.py).
 constexpr float kInvGamma22 = 1.0f / 2.2f;
 constexpr float kGammaMargin = 0x1p-20f;  // relative, ~8 ulp
+// to_u8(rclamp(y)) in three straight-line VALU ops: v = RN(y * 255), the hardware's saturating
+// float -> unsigned convert (v_cvt_u32_f32: NaN and negatives, -0 included, give 0; in-range values
+// truncate; values past 2^32 - 1 give 2^32 - 1), an unsigned min with 255.  Equal for every y:
+//  - y NaN: rclamp passes it on, v is NaN, !(v > 0) gives 0; the convert gives 0.
+//  - y < 0 (-inf included): rclamp gives 0, byte 0; here v <= -0 (an underflow keeps the sign), byte 0.
+//  - y = -0 or +0: rclamp keeps it, v = -0 or +0, !(v > 0) gives 0; the convert gives 0.
+//  - 0 < y <= 1: the same v in [0, 255] on both sides; v = 0 (underflow) gives 0 and v = 255 gives
+//    255 either way, anything between trunc(v).
+//  - y > 1 (+inf included): rclamp gives 1, byte 255; RN(. * 255) is monotone and RN(1 * 255) = 255,
+//    so v >= 255, the convert gives >= 255 and the min 255.
+// (The branches of to_u8 / rclamp compile to nested EXEC save / branch diamonds at -O1.)
+__device__ __forceinline__ uint32_t sat_u8(float y) {
+    uint32_t q;
+    asm("v_cvt_u32_f32_e32 %0, %1" : "=v"(q) : "v"(y * 255.0f));
+    return q < 255u ? q : 255u;
+}
 __device__ __forceinline__ uint32_t gamma22_u8(float c) {
     const float y = __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(c) * kInvGamma22);
     const float m = y * kGammaMargin;
-    const uint32_t a = to_u8(rclamp(y - m)), b = to_u8(rclamp(y + m));
+    const uint32_t a = sat_u8(y - m), b = sat_u8(y + m);
     // c = -inf: log2 gives NaN (byte 0) but powf(-inf, 1/2.2) = +inf (byte 255)
     if (__builtin_expect(a == b && c != -kInf, 1)) return a;
     return to_u8(rclamp(powf(c, kInvGamma22)));
 }
 
 // Map this launch's local row to the image row (band interleave, §8e).
+template <class LT = LaunchAny>
 __device__ __forceinline__ uint32_t image_row(const KParams& kp, uint32_t r) {
+    if constexpr (LT::kPlain) return r;
     if (kp.band_rows == 0) return r + kp.row0;
     const uint32_t b = r / kp.band_rows, w = r - b * kp.band_rows;
     const BandMap m{kp.band_rows, kp.nranks, kp.sky_bands, kp.root_bands, kp.peer_bands};
@@ -2320,6 +2358,7 @@ __device__ __forceinline__ uint32_t image_row(const KParams& kp, uint32_t r) {
 // SALU ops and a scalar load each).  Call with all 64 lanes active.  The host enables it only when
 // a tile's local rows are consecutive image rows (no band mapping, or bands of a multiple of the
 // tile height).
+template <class LT = LaunchAny>
 __device__ __forceinline__ uint32_t camera_tile_mask(const KParams& kp, const FrameCam& cm, uint32_t tx,
                                                      uint32_t ty) {
     const uint32_t sh = cm.tile_cull;
@@ -2330,12 +2369,12 @@ __device__ __forceinline__ uint32_t camera_tile_mask(const KParams& kp, const Fr
         // band heights are multiples of 8)
         bx = (tx << kp.tile_shift) >> sh;
         bx1 = ((tx << kp.tile_shift) + (1u << kp.tile_shift) - 1u) >> sh;
-        by = image_row(kp, ty * (64u >> kp.tile_shift)) >> sh;
+        by = image_row<LT>(kp, ty * (64u >> kp.tile_shift)) >> sh;
     } else {
         const uint32_t wave = sh == 3u ? (threadIdx.x >> 6) : 0u;
         bx = (blockIdx.x * 16u + (wave & 1u) * 8u) >> sh;
         bx1 = bx;
-        by = image_row(kp, blockIdx.y * 16u + (wave >> 1) * 8u) >> sh;
+        by = image_row<LT>(kp, blockIdx.y * 16u + (wave >> 1) * 8u) >> sh;
     }
     const uint32_t j = threadIdx.x & 63u;
     bool in = false;
@@ -2393,30 +2432,37 @@ __device__ __forceinline__ bool launch_indices_ok(const KParams& kp, unsigned lo
 // of a wave runs the sample loop (lanes past the image edge are idle but
 // present) so the culling reductions see converged waves.  CULL selects the
 // shadow-culled LAMBERT_SHADOW variant (the host picks it per scene).
-template <int MODE, class S, bool SINGLE = false, bool CULL = false>
+// LT: the launch traits (LaunchAny, LaunchPlain above).
+template <int MODE, class S, bool SINGLE = false, bool CULL = false, class LT = LaunchAny>
 __device__ __forceinline__ void ray_kernel_body(const KParams& kp, const S& sc, const Cull& cl,
                                                 uint32_t* __restrict__ out_rgba8, float4* __restrict__ out_f32,
                                                 unsigned long long* __restrict__ counters) {
+    constexpr bool kPlain = LT::kPlain;
+    static_assert(!kPlain || SINGLE, "a plain launch renders one sample per pixel");
+    const uint32_t debug = launch_debug<LT>(kp);
     const uint32_t lane = threadIdx.x & 63u, wave = kWg64 ? 0u : threadIdx.x >> 6;
     // RRTE_DEBUG bit 2 (diagnostics): every index this wave derives from the launch (list slot, tile,
     // frame) is range-checked before use; a violation sets a bit in the check word (counters[1], an
     // unused word of shard 0; rrte_hip_check_word) and the wave stops instead of touching memory
-    if ((kp.debug & 4u) && kWg64 && !launch_indices_ok(kp, counters)) return;
-    const LaunchTile tile = launch_tile(kp);
+    if ((debug & 4u) && kWg64 && !launch_indices_ok(kp, counters)) return;
+    LaunchTile tile = launch_tile(kp);
     if (!tile.run) return;
+    if constexpr (kPlain) tile.z = 0u;
     // frame tile.z of the launch: its camera, its output (multi-frame launches have no f32 output)
     const FrameCam& cm = kp.cam[tile.z];
-    if (kp.out_image_rows)
-        out_rgba8 = cm.out;
-    else if (out_rgba8 && tile.z)
-        out_rgba8 = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(out_rgba8) + tile.z * kp.frame_stride);
+    if constexpr (!kPlain) {
+        if (kp.out_image_rows)
+            out_rgba8 = cm.out;
+        else if (out_rgba8 && tile.z)
+            out_rgba8 = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(out_rgba8) + tile.z * kp.frame_stride);
+    }
     // RRTE_DEBUG bit 4 (diagnostics, tools/wave_times.py): per-wave start / duration from the 100 MHz
     // wall clock into the f32 buffer instead of colours
-    const bool stamps = (kp.debug & 16u) && out_f32;
+    const bool stamps = !kPlain && (debug & 16u) && out_f32;
     const uint32_t tiles_x = kWg64 ? kp.tiles_x : gridDim.x;
     // bit 5: only workgroup (debug >> 16) runs (its waves' durations alone on the GPU)
     const uint32_t brow = tile.y;
-    if ((kp.debug & 32u) && brow * tiles_x + tile.x != (kp.debug >> 16)) return;
+    if ((debug & 32u) && brow * tiles_x + tile.x != (debug >> 16)) return;
     const bool timed = stamps || (kp.tile_cost && tile.z == 0u);
     const uint64_t t_wave0 = timed ? wall_clock64() : 0ull;
     const uint32_t ts = kp.tile_shift;  // (kWg64: tile 1 << ts wide, 64 >> ts rows)
@@ -2424,8 +2470,8 @@ __device__ __forceinline__ void ray_kernel_body(const KParams& kp, const S& sc, 
     const uint32_t lr = kWg64 ? brow * (64u >> ts) + (lane >> ts) : brow * 16u + (wave >> 1) * 8u + (lane >> 3);
     bool live = x < kp.width && lr < kp.rows;
     const uint32_t xc = live ? x : 0u;
-    const uint32_t y = image_row(kp, live ? lr : 0u);
-    if ((kp.debug & 4u) && live && y >= kp.height) {  // (bit 2: a band mapping past the frame)
+    const uint32_t y = image_row<LT>(kp, live ? lr : 0u);
+    if ((debug & 4u) && live && y >= kp.height) {  // (bit 2: a band mapping past the frame)
         atomicOr(counters + 1, 8ull);
         live = false;
     }
@@ -2433,7 +2479,7 @@ __device__ __forceinline__ void ray_kernel_body(const KParams& kp, const S& sc, 
     uint32_t nshadow = 0;
     Col acc{0.0f, 0.0f, 0.0f, 1.0f};  // BLACK
     const uint32_t nsamples = SINGLE ? 1u : kp.spp;
-    const uint32_t pmask = camera_tile_mask(kp, cm, tile.x, tile.y);
+    const uint32_t pmask = camera_tile_mask<LT>(kp, cm, tile.x, tile.y);
     // camera ray of sample s (raytracer.rs:66-70): per-(pixel, sample) RNG stream, jitter, generate_ray
     auto camera_ray = [&](uint32_t s, uint32_t& st) {
         st = pcg_hash(pcg_hash(pcg_hash(kp.seed) ^ pix) ^ s);
@@ -2452,7 +2498,17 @@ __device__ __forceinline__ void ray_kernel_body(const KParams& kp, const S& sc, 
         acc.b = acc.b + c.b;
         acc.a = acc.a + c.a;
     };
-    if constexpr (MODE == RRTE_MODE_REFCOMPAT && !SINGLE) {
+    // All-miss tile: every object of the scene is in the rectangle table and none of their rectangles
+    // meets this tile, so no camera ray of the wave can hit anything (the bound camera_tile_mask
+    // culls single tests with).  Each sample then adds what the search adds for a miss -- the
+    // background, or BLACK at max_depth 0 -- without ray generation, search or shading; such lanes cast
+    // no shadow ray.  (pmask's bits past the table are set: only the table's bits count.)
+    const uint32_t tn = cm.tile_n;
+    const bool all_miss = cm.tile_cull != 0u && tn >= kp.num_prims && (pmask & (tn < 32u ? ~(~0u << tn) : ~0u)) == 0u;
+    if (all_miss) {
+        const Col c = kp.max_depth == 0 ? Col{0.0f, 0.0f, 0.0f, 1.0f} : Col{kp.bg[0], kp.bg[1], kp.bg[2], kp.bg[3]};
+        for (uint32_t s = 0; s < nsamples; ++s) accumulate(c);
+    } else if constexpr (MODE == RRTE_MODE_REFCOMPAT && !SINGLE) {
         // Path regeneration: one loop advances every lane's current path by one bounce; a lane
         // whose path ends adds its colour and starts its next sample at once.  A wave then costs
         // the largest per-lane total of bounces instead of the sum over samples of each sample's
@@ -2485,14 +2541,22 @@ __device__ __forceinline__ void ray_kernel_body(const KParams& kp, const S& sc, 
             Ray r = camera_ray(s, st);
             Col c{0.0f, 0.0f, 0.0f, 1.0f};
             if (MODE == RRTE_MODE_LAMBERT_SHADOW) {
-                c = shade_lambert<S, CULL>(sc, kp, cl, r, live, nshadow, pmask);
+                c = shade_lambert<S, CULL, LT>(sc, kp, cl, r, live, nshadow, pmask);
             } else if (live) {
                 c = ray_color_ref<S, SINGLE>(sc, kp, r, st, SINGLE ? pmask : ~0u);
             }
             accumulate(c);
         }
     }
-    if (live) {
+    if constexpr (kPlain) {
+        // inv_spp = 1 (x * 1 = x), gamma 2.2, RGBA8 in device memory at the packed rows: the general
+        // epilogue below with its run-time choices taken
+        if (live) {
+            const size_t o = (size_t)lr * kp.width + x;
+            out_rgba8[o] = gamma22_u8(acc.r) | (gamma22_u8(acc.g) << 8) | (gamma22_u8(acc.b) << 16) |
+                           (sat_u8(acc.a) << 24);
+        }
+    } else if (live) {
         acc.r = acc.r * kp.inv_spp;
         acc.g = acc.g * kp.inv_spp;
         acc.b = acc.b * kp.inv_spp;

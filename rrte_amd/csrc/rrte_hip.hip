@@ -29,6 +29,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../include/rrte_hip_jit.h"
 #include "../../include/rrte_hip_mesh.h"
 #include "../../include/rrte_hip_refit.h"
 #include "bvh.hpp"
@@ -216,6 +217,9 @@ struct rrte_ctx {
     uint32_t env_debug = 0;       // RRTE_DEBUG ablation bits
     int env_cull = -1;            // RRTE_CULL: -1 unset, 0 off, 1 on
     bool env_tile_cull = true;    // RRTE_TILE_CULL=0: no camera-ray tile culling (A/B, tests)
+    bool env_jit_plain = true;    // RRTE_JIT_PLAIN=0: specialised kernels always through the general entry (A/B, tests)
+    uint32_t last_entry = 0;      // the last ray launch's kernel (rrte_hip_jit_entry): RRTE_ENTRY_*
+    bool host_out = false;        // the launch being issued writes a pinned host frame (render_common's zero-copy path)
     bool env_force_gather = false;  // RRTE_FORCE_GATHER=1
     bool env_gather_rgba = false;   // RRTE_GATHER_RGB24=0: gather slabs always RGBA8
     bool env_band_sky = true;       // RRTE_BAND_SKY=0: the plain band interleave (band_layout)
@@ -1141,8 +1145,9 @@ KParams make_params(const rrte_ctx* c, const rrte_scene_ir* s, const rrte_render
 // that meets the sphere's disc there, so x lies between the tangents of that disc (likewise y in the
 // yz plane).  Double precision, then 2 pixels of margin per side -- orders of magnitude above the f32
 // error of the device's ray directions (~1e-6 of the field of view) and of random jitter's extent
-// (inside the pixel).  A sphere that contains the eye or reaches the plane z = 0 keeps the whole
-// frame.  Bit-identical results by construction: a skipped test is one every lane would miss
+// (inside the pixel).  A sphere that contains the eye keeps the whole frame; one that reaches the
+// plane z = 0 from outside the eye keeps every column and the rows from its silhouette's top down.
+// Bit-identical results by construction: a skipped test is one every lane would miss
 // (tests/test_gpu_parity.py test_camera_tile_culling_is_exact).
 void fill_tile_rects_uncached(const rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_params* p, KParams& kk);
 
@@ -1217,7 +1222,41 @@ void tile_rects(bool enabled, const std::vector<float4>& bounds, const rrte_scen
         double v[3];
         to_cam(w, v);
         const bool finite = std::isfinite(R) && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
-        if (finite && R >= 0.0 && v[2] < -R * 1.001 - 1e-6) {  // entirely in front of the eye (z < 0)
+        const bool in_front = finite && R >= 0.0 && v[2] < -R * 1.001 - 1e-6;
+        // A sphere that reaches the eye plane but keeps the eye outside (a ground sphere under the
+        // camera): its top row from a tangent plane of the cone of directions that meet it.  Let w be
+        // the unit vector of the image plane (x, y) towards the centre and r the centre's distance
+        // from the view axis.  A camera ray (x, s, -1) t projects, along the direction of the image
+        // plane normal to w, onto the half-line (q, -1) t with q = (x, s) . w, and a ray that meets the
+        // sphere then meets its disc there (centre (r, cz), radius R: dropping a coordinate only
+        // brings a point closer to the centre).  With the origin outside the disc (the eye outside
+        // the sphere) the directions that meet it lie within beta = asin(R / D) of the centre's
+        // direction alpha = atan2(r, -cz) in [0, 180] degrees, measured from the view axis towards w;
+        // a camera ray is at atan(q) in (-90, 90), so a hit needs q >= tan(alpha - beta) =: t -- for
+        // alpha - beta >= 90 degrees no camera ray hits at all, at or below -90 nothing is known.  With
+        // w pointing down the image (wy < 0) that reads s <= (x wx - t) / -wy, at most
+        // (hw |wx| - t) / -wy over the frame's columns |x| <= hw: the horizon's highest point.
+        // Only the top is bounded; double precision and the margin of the other sides.  The eye keeps
+        // a distance of 1e-4 R from the surface: closer, the device's f32 discriminant is too coarse
+        // for a bound of two pixels.
+        const double dist = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), rad = std::sqrt(v[0] * v[0] + v[1] * v[1]);
+        if (finite && R > 0.0 && !in_front && dist > R * 1.0001 && rad > 1e-9 * dist) {
+            const double kHalfPi = 1.57079632679489661923, lo = std::atan2(rad, -v[2]) - std::asin(R / dist);
+            const double wx = v[0] / rad, wy = v[1] / rad, H = p->height;
+            if (lo > kHalfPi - 1e-9) {
+                if (lo > kHalfPi + 1e-9) rect = 0xFFu | (0xFFu << 16);  // behind the eye: no block (as below)
+            } else if (lo > -kHalfPi + 1e-9 && wy < -1e-9) {
+                const double s_top = (hw * std::fabs(wx) - std::tan(lo)) / -wy;
+                const double py0 = (1.0 - s_top / hh) * H * 0.5 - 0.5 - margin;
+                if (py0 > H - 1.0) {
+                    rect = 0xFFu | (0xFFu << 16);
+                } else if (std::isfinite(py0) && py0 > 0.0) {
+                    const uint32_t by0 = (uint32_t)std::min<double>(std::floor(py0 / (double)(1u << sh)), (double)(nby - 1));
+                    rect = 0u | ((nbx - 1) << 8) | (by0 << 16) | ((nby - 1) << 24);
+                }
+            }
+        }
+        if (in_front) {  // entirely in front of the eye (z < 0)
             // tangent slopes of the disc (centre (c, -d), radius R, d > R) seen from the origin:
             // tan(alpha -/+ beta) with tan alpha = c / d and tan beta = R / sqrt(D^2 - R^2), by the
             // angle-sum identity (no trigonometry: this runs per object for every new camera).  The
@@ -1850,6 +1889,20 @@ void launch_generic(uint32_t need, dim3 grid, dim3 block, hipStream_t st, const 
         hipLaunchKernelGGL((ray_kernel<MODE, CULL, kFeatEvery>), grid, block, 0, st, k, sv, cl, d_rgba, d_f32, ctr);
 }
 
+// Whether a launch of the specialised kernel `jk` meets every assumption of its plain entry
+// (ray_kernels.hpp LaunchPlain): one frame into the RGBA8 device buffer `d_rgba` alone, rows packed from
+// image row 0 with no band map, no debug bit, gamma 2.2, one sample per pixel (SINGLE kernels only
+// have the entry) and 64-thread workgroups.  Gather slabs, rank shares, multi-frame batches, f32
+// frames, zero-copy frames (rrte_ctx::host_out), RRTE_DEBUG and other gammas
+// fail one of the tests and take the general entry; RRTE_JIT_PLAIN=0 sends everything there.
+bool plain_launch(const rrte_ctx* c, const JitKernel* jk, const LaunchPlan& L, const uint32_t* d_rgba,
+                  const float4* d_f32) {
+    const KParams& k = L.k;
+    return c->env_jit_plain && jk->fn_plain && L.single && !c->env_wg256 && d_rgba && !d_f32 && !c->host_out &&
+           k.nframes == 1 && k.band_rows == 0 && k.row0 == 0 && k.out_image_rows == 0 && k.debug == 0 &&
+           !(k.flags & (kFlagSlabRgb24 | kFlagHostStore)) && k.inv_gamma == kInvGamma22 && k.inv_spp == 1.0f;
+}
+
 // Launch plan `L` (L.k.nframes frames) on `st`; the cached scene is the plan's.
 rrte_status issue_launch(rrte_ctx* c, LaunchPlan& L, uint32_t* d_rgba, float4* d_f32, hipStream_t st) {
     if (L.gy == 0) return RRTE_OK;
@@ -1883,7 +1936,11 @@ rrte_status issue_launch(rrte_ctx* c, LaunchPlan& L, uint32_t* d_rgba, float4* d
         void* args[] = {&L.k, &cl, &mv, &d_rgba, &d_f32, &ctr, &vals};
         if (c->hpa_cur) hsa.lap(13);
         HostSection hs(c);
-        if (c->env_wg256)
+        const bool plain = plain_launch(c, jk, L, d_rgba, d_f32);
+        c->last_entry = plain ? RRTE_ENTRY_PLAIN : RRTE_ENTRY_GENERAL;
+        if (plain)
+            HIPCHK(c, hipModuleLaunchKernel(jk->fn_plain, grid.x, grid.y, grid.z, kBlockThreads, 1, 1, 0, st, args, nullptr));
+        else if (c->env_wg256)
             HIPCHK(c, hipModuleLaunchKernel(jk->fn, (L.k.width + 15) / 16, (L.k.rows + 15) / 16, L.k.nframes, 256, 1, 1,
                                             0, st, args, nullptr));
         else
@@ -1891,6 +1948,7 @@ rrte_status issue_launch(rrte_ctx* c, LaunchPlan& L, uint32_t* d_rgba, float4* d
         hs.lap(c->hpa_cur ? 14 : 8);
         return finish_tile_order(c, L, profile, st);
     }
+    c->last_entry = RRTE_ENTRY_GENERIC;
     SceneView sv{c->d_prims, c->d_mats, c->d_lights, c->d_nodes, L.num_prims, L.num_lights, L.num_materials,
                  c->mesh_view};
     const KParams& k = L.k;
@@ -2075,9 +2133,11 @@ rrte_status render_common(rrte_ctx* c, const rrte_scene_ir* s, const rrte_render
     } else {
         HIPCHK(c, hipEventRecord(c->ev0, c->stream));
         if (zc) c->tile_shift = c->zc_tile_shift;  // whole 128-B lines per wave across PCIe
+        c->host_out = zc != nullptr;
         r = launch(c, s, p, p->height, zc ? zc : c->d_rgba, outf ? c->d_f32 : nullptr, c->stream,
                    zc && c->env_zc_system_store ? kFlagHostStore : 0u, 0u, zc ? rrte_ctx::kZcProf : 0);
         c->tile_shift = 3;
+        c->host_out = false;
         if (r == RRTE_OK) r = hipEventRecord(c->ev1, c->stream) == hipSuccess ? RRTE_OK : RRTE_HIP_ERROR;
     }
     c->nranks = nr;
@@ -2149,6 +2209,7 @@ rrte_status rrte_hip_create(int device, rrte_ctx** out) {
     if (const char* d = getenv("RRTE_DEBUG")) c->env_debug = (uint32_t)strtoul(d, nullptr, 0);
     c->env_cull = env_cull_setting();
     if (const char* t = getenv("RRTE_TILE_CULL")) c->env_tile_cull = t[0] != '0';
+    if (const char* t = getenv("RRTE_JIT_PLAIN")) c->env_jit_plain = t[0] != '0';
     if (const char* g = getenv("RRTE_FORCE_GATHER")) c->env_force_gather = g[0] == '1';
     if (const char* g = getenv("RRTE_HOST_PROFILE")) c->host_prof = g[0] == '1';
     if (const char* g = getenv("RRTE_TRACE")) c->trace = g[0] == '1';
@@ -2430,6 +2491,13 @@ rrte_status rrte_hip_check_word(rrte_ctx* c, uint64_t* word) {
     return RRTE_OK;
 }
 
+// include/rrte_hip_jit.h
+rrte_status rrte_hip_jit_entry(rrte_ctx* c, uint32_t* entry) {
+    if (!c || !entry) return RRTE_INVALID_ARG;
+    *entry = c->last_entry;
+    return RRTE_OK;
+}
+
 // include/rrte_hip_mesh.h
 rrte_status rrte_hip_mesh_info(rrte_ctx* c, rrte_mesh_info* out) {
     if (!c || !out) return RRTE_INVALID_ARG;
@@ -2686,6 +2754,28 @@ rrte_status rrte_hip_band_layout(const rrte_scene_ir* s, const rrte_render_param
     *sky_bands = m.sky;
     *root_bands = m.root_bands;
     *peer_bands = m.peer_bands;
+    return RRTE_OK;
+}
+
+// include/rrte_hip_jit.h
+rrte_status rrte_hip_tile_rects(const rrte_scene_ir* s, const rrte_render_params* p, uint32_t* tile_shift,
+                                uint32_t* count, uint32_t* rects) {
+    if (!s || !p || !tile_shift || !count || !rects || p->width == 0 || p->height == 0) return RRTE_INVALID_ARG;
+    if ((s->num_prims && !s->prims) || (s->num_mesh_indices && !s->mesh_indices) ||
+        (s->num_mesh_vertices && !s->mesh_vertices))
+        return RRTE_INVALID_ARG;
+    std::vector<DPrim> prims;
+    std::vector<DMaterial> mats;
+    std::vector<DLight> lights;
+    std::vector<float4> bounds;
+    lower_scene(s, prims, mats, lights, &bounds);
+    MeshData md;
+    build_mesh_bvhs(s, prims.data(), md, bounds.data());
+    KParams k{};
+    tile_rects(true, bounds, s, p, k);  // (k.band_rows 0: a whole frame on one context)
+    *tile_shift = k.cam[0].tile_cull;
+    *count = k.cam[0].tile_cull ? k.cam[0].tile_n : 0u;
+    for (uint32_t i = 0; i < *count; ++i) rects[i] = k.cam[0].tile_rect[i];
     return RRTE_OK;
 }
 
