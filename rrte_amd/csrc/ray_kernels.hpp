@@ -94,22 +94,6 @@ __device__ __forceinline__ void for_each_prim(const S& sc, F&& f) {
         for (uint32_t i = 0; i < sc.num_prims; ++i) f(i);
     }
 }
-#ifndef RRTE_EXP_PRIM_ORDER
-#define RRTE_EXP_PRIM_ORDER 0
-#endif
-template <uint32_t I, uint32_t N, class F>
-__device__ __forceinline__ void static_for_rev(F& f) {
-    if constexpr (I < N) {
-        f(UC<N - 1u - I>{});
-        static_for_rev<I + 1, N>(f);
-    }
-}
-// EXPERIMENT: object order of the closest-hit (bit 0) / any-hit (bit 1) searches, reversed.
-template <int BIT, class S, class F>
-__device__ __forceinline__ void for_each_prim_exp(const S& sc, F&& f) {
-    if constexpr (S::kStatic && (RRTE_EXP_PRIM_ORDER & BIT)) static_for_rev<0, S::num_prims>(f);
-    else for_each_prim(sc, f);
-}
 // Scene-specialised kernels come in two kinds (jit.hip).  FULL (S::kTopo false): every scene record
 // is a static constexpr array, so all scene constants fold into the code.  TOPOLOGY (S::kTopo true):
 // only the scene's structure is compile-time -- object kinds, materials and SDF node ranges, node
@@ -212,72 +196,67 @@ __device__ __forceinline__ void for_each_light(const S& sc, F&& f) {
 }
 
 // ------------------------------------------------------------- SDF program
-// The SDF evaluation is templated on its guard policy G (device_scene.hpp: GuardNow / GuardDefer /
-// GuardSlow) for its square roots and constant divides; every policy returns the same bits.
-template <class G>
-__device__ __forceinline__ float len2f(G& g, float a, float b) { return g.sqrt(a * a + b * b); }
-template <class G>
-__device__ __forceinline__ float len3f(G& g, float a, float b, float c) { return g.sqrt((a * a + b * b) + c * c); }
+__device__ __forceinline__ float len2f(float a, float b) { return sqrt_rn(a * a + b * b); }
+__device__ __forceinline__ float len3f(float a, float b, float c) { return sqrt_rn((a * a + b * b) + c * c); }
 
-template <class G>
-__device__ __forceinline__ float sdf_leaf(G& g, uint32_t op, const float* __restrict__ f, f3 p) {
+__device__ __forceinline__ float sdf_leaf(uint32_t op, const float* __restrict__ f, f3 p) {
     f3 q = vsub(p, V(f[0], f[1], f[2]));
     switch (op) {
     case RRTE_SDF_SPHERE:
-        return len3f(g, q.x, q.y, q.z) - f[3];
+        return len3f(q.x, q.y, q.z) - f[3];
     case RRTE_SDF_BOX: {
         float dx = fabsf(q.x) - f[4] * 0.5f, dy = fabsf(q.y) - f[5] * 0.5f, dz = fabsf(q.z) - f[6] * 0.5f;
-        float outside = len3f(g, smx(dx, 0.0f), smx(dy, 0.0f), smx(dz, 0.0f));
+        float outside = len3f(smx(dx, 0.0f), smx(dy, 0.0f), smx(dz, 0.0f));
         float inside = smn(smx(dx, smx(dy, dz)), 0.0f);
         return outside + inside;
     }
     case RRTE_SDF_CYLINDER: {
-        float dx = len2f(g, q.x, q.z) - f[3], dy = fabsf(q.y) - f[4] * 0.5f;
-        return smn(smx(dx, dy), 0.0f) + len2f(g, smx(dx, 0.0f), smx(dy, 0.0f));
+        float dx = len2f(q.x, q.z) - f[3], dy = fabsf(q.y) - f[4] * 0.5f;
+        return smn(smx(dx, dy), 0.0f) + len2f(smx(dx, 0.0f), smx(dy, 0.0f));
     }
     case RRTE_SDF_PRISM: {
         float a = smx(fabsf(q.x) * 0.866025f + q.y * 0.5f, -q.y) - f[5] * 0.25f;
         return smx(fabsf(q.z) - f[6] * 0.5f, a);
     }
     case RRTE_SDF_TORUS: {
-        float qx = len2f(g, q.x, q.z) - f[3];
-        return len2f(g, qx, q.y) - f[4];
+        float qx = len2f(q.x, q.z) - f[3];
+        return len2f(qx, q.y) - f[4];
     }
     case RRTE_SDF_TUBE: {
-        float rad = len2f(g, q.x, q.z);
+        float rad = len2f(q.x, q.z);
         float mid = (f[3] + f[4]) * 0.5f, half = (f[3] - f[4]) * 0.5f;
         float dx = fabsf(rad - mid) - half, dy = fabsf(q.y) - f[5] * 0.5f;
-        return smn(smx(dx, dy), 0.0f) + len2f(g, smx(dx, 0.0f), smx(dy, 0.0f));
+        return smn(smx(dx, dy), 0.0f) + len2f(smx(dx, 0.0f), smx(dy, 0.0f));
     }
     case RRTE_SDF_RING: {
-        float qx = len2f(g, q.x, q.y) - f[3];
-        return len2f(g, qx, q.z) - f[4];
+        float qx = len2f(q.x, q.y) - f[3];
+        return len2f(qx, q.z) - f[4];
     }
     case RRTE_SDF_CONE: {
         float r1 = f[3], hh = f[4] * 0.5f;
-        float qx = len2f(g, q.x, q.z), qy = q.y;
+        float qx = len2f(q.x, q.z), qy = q.y;
         float k2x = -r1, k2y = hh * 2.0f;
         float cax = qx - smn(qx, (qy < 0.0f) ? r1 : 0.0f);
         float cay = fabsf(qy) - hh;
         float k1mqx = 0.0f - qx, k1mqy = hh - qy;
         float tnum = k1mqx * k2x + k1mqy * k2y;
         float tden = k2x * k2x + k2y * k2y;
-        float t = sclamp(g.div(tnum, tden), 0.0f, 1.0f);
+        float t = sclamp(div_rn(tnum, tden), 0.0f, 1.0f);
         float cbx = (qx - 0.0f) + k2x * t;
         float cby = (qy - hh) + k2y * t;
         float s = (cbx < 0.0f && cay < 0.0f) ? -1.0f : 1.0f;
         float da = cax * cax + cay * cay, db = cbx * cbx + cby * cby;
-        return s * g.sqrt(smn(da, db));
+        return s * sqrt_rn(smn(da, db));
     }
     case RRTE_SDF_CAPSULE: {
         float hh = f[4] * 0.5f;
         float y = q.y - sclamp(q.y, -hh, hh);
-        return len3f(g, q.x, y, q.z) - f[3];
+        return len3f(q.x, y, q.z) - f[3];
     }
     case RRTE_SDF_ELLIPSOID: {
         float rx = f[4], ry = f[5], rz = f[6];
-        float k0 = len3f(g, g.div(q.x, rx), g.div(q.y, ry), g.div(q.z, rz));
-        float k1 = len3f(g, g.div(q.x, rx * rx), g.div(q.y, ry * ry), g.div(q.z, rz * rz));
+        float k0 = len3f(div_rn(q.x, rx), div_rn(q.y, ry), div_rn(q.z, rz));
+        float k1 = len3f(div_rn(q.x, rx * rx), div_rn(q.y, ry * ry), div_rn(q.z, rz * rz));
         if (!(k1 > 0.0f)) return -smn(rx, smn(ry, rz));
         return k0 * (k0 - 1.0f) / k1;
     }
@@ -287,16 +266,14 @@ __device__ __forceinline__ float sdf_leaf(G& g, uint32_t op, const float* __rest
 }
 
 // smooth_min (README.md:485-488)
-template <class G>
-__device__ __forceinline__ float smin(G& g, float a, float b, float k) {
-    float h = sclamp(0.5f + g.div(0.5f * (b - a), k), 0.0f, 1.0f);
+__device__ __forceinline__ float smin(float a, float b, float k) {
+    float h = sclamp(0.5f + div_rn(0.5f * (b - a), k), 0.0f, 1.0f);
     float om = 1.0f - h;
     return (a * h + b * om) - (k * h) * om;
 }
 
-template <class G>
-__device__ __forceinline__ f3 sdf_deform(G& g, uint32_t op, const uint32_t* __restrict__ iarg,
-                                         const float* __restrict__ f, f3 p) {
+__device__ __forceinline__ f3 sdf_deform(uint32_t op, const uint32_t* __restrict__ iarg, const float* __restrict__ f,
+                                         f3 p) {
     f3 c = V(f[0], f[1], f[2]);
     f3 q = vsub(p, c);
     switch (op) {
@@ -315,7 +292,7 @@ __device__ __forceinline__ f3 sdf_deform(G& g, uint32_t op, const uint32_t* __re
     case RRTE_SDF_TAPER: {
         uint32_t ax = iarg[0];
         uint32_t u = (ax + 1) % 3, w = (ax + 2) % 3;
-        float t = sclamp(g.div(comp(q, ax) + f[5] * 0.5f, f[5]), 0.0f, 1.0f);
+        float t = sclamp(div_rn(comp(q, ax) + f[5] * 0.5f, f[5]), 0.0f, 1.0f);
         float s = f[3] + (f[4] - f[3]) * t;
         q = setcomp(q, u, comp(q, u) / s);
         q = setcomp(q, w, comp(q, w) / s);
@@ -360,11 +337,11 @@ __device__ __forceinline__ f3 sdf_deform(G& g, uint32_t op, const uint32_t* __re
 // replace it, POP_POINT restores it).
 // (op and the integer arguments separately from the float arguments: a topology kernel has the
 // first two at compile time and reads the third.)
-template <class G, bool DEFORM = true>
-__device__ __forceinline__ void sdf_node_step(G& g, uint32_t op, const uint32_t* iargs, const float* fargs, float* vs,
-                                              f3* ps, uint32_t& sp, uint32_t& pp, f3& p) {
+template <bool DEFORM = true>
+__device__ __forceinline__ void sdf_node_step(uint32_t op, const uint32_t* iargs, const float* fargs, float* vs, f3* ps,
+                                              uint32_t& sp, uint32_t& pp, f3& p) {
     if (op < 32) {
-        vs[sp] = sdf_leaf(g, op, fargs, p);
+        vs[sp] = sdf_leaf(op, fargs, p);
         ++sp;
     } else if (op < 64) {
         float b = vs[sp - 1], a = vs[sp - 2], r;
@@ -373,9 +350,9 @@ __device__ __forceinline__ void sdf_node_step(G& g, uint32_t op, const uint32_t*
         case RRTE_SDF_UNION: r = smn(a, b); break;
         case RRTE_SDF_DIFFERENCE: r = smx(a, -b); break;
         case RRTE_SDF_INTERSECTION: r = smx(a, b); break;
-        case RRTE_SDF_SMOOTH_UNION: r = smin(g, a, b, k); break;
-        case RRTE_SDF_SMOOTH_DIFFERENCE: r = -smin(g, -a, b, k); break;
-        default: r = -smin(g, -a, -b, k); break;
+        case RRTE_SDF_SMOOTH_UNION: r = smin(a, b, k); break;
+        case RRTE_SDF_SMOOTH_DIFFERENCE: r = -smin(-a, b, k); break;
+        default: r = -smin(-a, -b, k); break;
         }
         sp -= 2;
         vs[sp] = r;
@@ -384,7 +361,7 @@ __device__ __forceinline__ void sdf_node_step(G& g, uint32_t op, const uint32_t*
         if (op < 96) {
             ps[pp] = p;
             ++pp;
-            p = sdf_deform(g, op, iargs, fargs, p);
+            p = sdf_deform(op, iargs, fargs, p);
         } else {
             --pp;
             p = ps[pp];
@@ -399,8 +376,7 @@ __device__ __forceinline__ void sdf_node_step(G& g, uint32_t op, const uint32_t*
 // difference: h computed with L is 1, so h(b) is 1 by monotone rounding, and with b >= L >= 0 the
 // formula reduces to a + 0 / -(-a + 0)).  Wave-uniform: taken only when every active lane may take
 // it, so the result never depends on the guard.
-template <class G>
-__device__ __forceinline__ bool sdf_guard(G& gp, uint32_t gop, const float* gf, float a, f3 p, float& r) {
+__device__ __forceinline__ bool sdf_guard(uint32_t gop, const float* gf, float a, f3 p, float& r) {
     const float dx = p.x - gf[4], dy = p.y - gf[5], dz = p.z - gf[6];
     const float s = __builtin_amdgcn_sqrtf((dx * dx + dy * dy) + dz * dz);
     const float L = gf[8] * (s - gf[7]);
@@ -415,12 +391,12 @@ __device__ __forceinline__ bool sdf_guard(G& gp, uint32_t gop, const float* gf, 
         r = a;
         break;
     case RRTE_SDF_SMOOTH_UNION:
-        ok = ok && sclamp(0.5f + gp.div(0.5f * (L - a), gf[0]), 0.0f, 1.0f) == 1.0f;
+        ok = ok && sclamp(0.5f + div_rn(0.5f * (L - a), gf[0]), 0.0f, 1.0f) == 1.0f;
         r = a + 0.0f;
         break;
     default: {  // RRTE_SDF_SMOOTH_DIFFERENCE: -smin(-a, b, k)
         const float na = -a;
-        ok = ok && sclamp(0.5f + gp.div(0.5f * (L - na), gf[0]), 0.0f, 1.0f) == 1.0f;
+        ok = ok && sclamp(0.5f + div_rn(0.5f * (L - na), gf[0]), 0.0f, 1.0f) == 1.0f;
         r = -(na + 0.0f);
         break;
     }
@@ -441,8 +417,7 @@ struct SdfProgramT {
     static constexpr int kPlan = 0;  // (sdf_parts_plan: no part-wise secant exit)
     const rrte_sdf_node* __restrict__ nodes;
     uint32_t count;
-    template <class G>
-    __device__ __forceinline__ float eval(f3 p, G& g) const {
+    __device__ __forceinline__ float operator()(f3 p) const {
         // The two shapes most objects have -- one leaf, or two leaves under one CSG op (no deformer,
         // no guard: guards need operands of >= 2 leaves) -- evaluate without the stack machine: no
         // per-node loop, no dynamically indexed stack, and the nodes' scalar loads do not depend on
@@ -451,20 +426,20 @@ struct SdfProgramT {
         // (the program's nodes are wave-uniform: read through load_uniform, scalar loads)
         const rrte_sdf_node n0 = load_uniform(nodes);
         const uint32_t op0 = n0.op;
-        if (RRTE_SDF_FASTPATH && count == 1u && op0 < 32u) return sdf_leaf(g, op0, n0.f, p);
+        if (RRTE_SDF_FASTPATH && count == 1u && op0 < 32u) return sdf_leaf(op0, n0.f, p);
         const rrte_sdf_node n1 = load_uniform(nodes + (count > 1u ? 1u : 0u));
         const rrte_sdf_node n2 = load_uniform(nodes + (count > 2u ? 2u : 0u));
         if (RRTE_SDF_FASTPATH && count == 3u && op0 < 32u && n1.op < 32u && n2.op >= 32u && n2.op < 64u && n1.i[2] == 0u) {
-            const float a = sdf_leaf(g, op0, n0.f, p);
-            const float b = sdf_leaf(g, n1.op, n1.f, p);
+            const float a = sdf_leaf(op0, n0.f, p);
+            const float b = sdf_leaf(n1.op, n1.f, p);
             const float k = n2.f[0];
             switch (n2.op) {
             case RRTE_SDF_UNION: return smn(a, b);
             case RRTE_SDF_DIFFERENCE: return smx(a, -b);
             case RRTE_SDF_INTERSECTION: return smx(a, b);
-            case RRTE_SDF_SMOOTH_UNION: return smin(g, a, b, k);
-            case RRTE_SDF_SMOOTH_DIFFERENCE: return -smin(g, -a, b, k);
-            default: return -smin(g, -a, -b, k);
+            case RRTE_SDF_SMOOTH_UNION: return smin(a, b, k);
+            case RRTE_SDF_SMOOTH_DIFFERENCE: return -smin(-a, b, k);
+            default: return -smin(-a, -b, k);
             }
         }
         float vs[RRTE_SDF_MAX_STACK];
@@ -476,19 +451,15 @@ struct SdfProgramT {
             float r;
             if (link != 0u) {
                 const rrte_sdf_node gn = load_uniform(nodes + (link - 1u));
-                if (sdf_guard(g, gn.op, gn.f, vs[sp - 1], p, r)) {
+                if (sdf_guard(gn.op, gn.f, vs[sp - 1], p, r)) {
                     vs[sp - 1] = r;
                     i = link - 1u;  // continue after the op
                     continue;
                 }
             }
-            sdf_node_step<G, (F & kFeatDeform) != 0u>(g, ni.op, ni.i, ni.f, vs, ps, sp, pp, p);
+            sdf_node_step<(F & kFeatDeform) != 0u>(ni.op, ni.i, ni.f, vs, ps, sp, pp, p);
         }
         return vs[0];
-    }
-    __device__ __forceinline__ float operator()(f3 p) const {
-        GuardNow g;
-        return eval(p, g);
     }
 };
 using SdfProgram = SdfProgramT<kFeatAll>;
@@ -511,12 +482,7 @@ struct SdfLeafProgram {
         for (int j = 0; j < 7; ++j) k += a.f[j] < 0.0f ? -a.f[j] : a.f[j];
         return k;
     }
-    template <class G>
-    __device__ __forceinline__ float eval(f3 p, G& g) const { return sdf_leaf(g, OP, a.f, p); }
-    __device__ __forceinline__ float operator()(f3 p) const {
-        GuardNow g;
-        return eval(p, g);
-    }
+    __device__ __forceinline__ float operator()(f3 p) const { return sdf_leaf(OP, a.f, p); }
 };
 // Leaves whose one-leaf program is convex and 1-Lipschitz whatever their sizes (sdf_convex; the cone
 // only for radius and height > 0, a runtime fact, so not here): the secant early miss applies.
@@ -587,9 +553,8 @@ constexpr TopoNode node_topo() {
     if constexpr (S::kTopo) return S::topo_nodes[K];
     else return TopoNode{S::nodes[K].op, {S::nodes[K].i[0], S::nodes[K].i[1], S::nodes[K].i[2]}};
 }
-template <class S, uint32_t FIRST, uint32_t I, uint32_t END, bool CHECK, class G>
-__device__ __forceinline__ void sdf_static_range(const S& sc, G& gp, float* vs, f3* ps, uint32_t& sp, uint32_t& pp,
-                                                 f3& p) {
+template <class S, uint32_t FIRST, uint32_t I, uint32_t END, bool CHECK>
+__device__ __forceinline__ void sdf_static_range(const S& sc, float* vs, f3* ps, uint32_t& sp, uint32_t& pp, f3& p) {
     if constexpr (I < END) {
         constexpr TopoNode tn = node_topo<S, FIRST + I>();
         constexpr uint32_t link = tn.i[2];
@@ -599,23 +564,23 @@ __device__ __forceinline__ void sdf_static_range(const S& sc, G& gp, float* vs, 
             bool taken;
             if constexpr (S::kTopo) {
                 const NodeArgs na = load_uniform(reinterpret_cast<const NodeArgs*>(sc.nodes[FIRST + link - 1u].f));
-                taken = sdf_guard(gp, gop, na.f, vs[sp - 1], p, r);
+                taken = sdf_guard(gop, na.f, vs[sp - 1], p, r);
             } else {
                 constexpr rrte_sdf_node g = S::nodes[FIRST + link - 1u];
-                taken = sdf_guard(gp, gop, g.f, vs[sp - 1], p, r);
+                taken = sdf_guard(gop, g.f, vs[sp - 1], p, r);
             }
             if (taken) vs[sp - 1] = r;
-            else sdf_static_range<S, FIRST, I, link, false>(sc, gp, vs, ps, sp, pp, p);
-            sdf_static_range<S, FIRST, link, END, true>(sc, gp, vs, ps, sp, pp, p);
+            else sdf_static_range<S, FIRST, I, link, false>(sc, vs, ps, sp, pp, p);
+            sdf_static_range<S, FIRST, link, END, true>(sc, vs, ps, sp, pp, p);
         } else {
             if constexpr (S::kTopo) {
                 const NodeArgs na = load_uniform(reinterpret_cast<const NodeArgs*>(sc.nodes[FIRST + I].f));
-                sdf_node_step(gp, tn.op, tn.i, na.f, vs, ps, sp, pp, p);
+                sdf_node_step(tn.op, tn.i, na.f, vs, ps, sp, pp, p);
             } else {
                 constexpr rrte_sdf_node n = S::nodes[FIRST + I];
-                sdf_node_step(gp, n.op, n.i, n.f, vs, ps, sp, pp, p);
+                sdf_node_step(n.op, n.i, n.f, vs, ps, sp, pp, p);
             }
-            sdf_static_range<S, FIRST, I + 1u, END, true>(sc, gp, vs, ps, sp, pp, p);
+            sdf_static_range<S, FIRST, I + 1u, END, true>(sc, vs, ps, sp, pp, p);
         }
     }
 }
@@ -635,17 +600,12 @@ struct SdfStaticProgram {
             return k;
         }
     }
-    template <class G>
-    __device__ __forceinline__ float eval(f3 p, G& g) const {
+    __device__ __forceinline__ float operator()(f3 p) const {
         float vs[RRTE_SDF_MAX_STACK];
         f3 ps[RRTE_SDF_MAX_POINT_STACK];
         uint32_t sp = 0, pp = 0;
-        sdf_static_range<S, FIRST, 0u, COUNT, true>(sc, g, vs, ps, sp, pp, p);
+        sdf_static_range<S, FIRST, 0u, COUNT, true>(sc, vs, ps, sp, pp, p);
         return vs[0];
-    }
-    __device__ __forceinline__ float operator()(f3 p) const {
-        GuardNow g;
-        return eval(p, g);
     }
 };
 
@@ -700,25 +660,19 @@ struct SdfPartsProgram {
         constexpr float k = sdf_leaf_scale(S::nodes + FIRST, 3u);
         return k;
     }
-    template <class G>
-    __device__ __forceinline__ float eval_parts(f3 p, G& g, float& a, float& b) const {
+    __device__ __forceinline__ float eval_parts(f3 p, float& a, float& b) const {
         constexpr rrte_sdf_node na = S::nodes[FIRST], nb = S::nodes[FIRST + 1], no = S::nodes[FIRST + 2];
-        a = sdf_leaf(g, na.op, na.f, p);
-        b = sdf_leaf(g, nb.op, nb.f, p);
+        a = sdf_leaf(na.op, na.f, p);
+        b = sdf_leaf(nb.op, nb.f, p);
         const float k = no.f[0];
         if constexpr (kOp == RRTE_SDF_UNION) return smn(a, b);
         else if constexpr (kOp == RRTE_SDF_DIFFERENCE) return smx(a, -b);
-        else if constexpr (kOp == RRTE_SDF_SMOOTH_UNION) return smin(g, a, b, k);
-        else return -smin(g, -a, b, k);  // RRTE_SDF_SMOOTH_DIFFERENCE
-    }
-    template <class G>
-    __device__ __forceinline__ float eval(f3 p, G& g) const {
-        float a, b;
-        return eval_parts(p, g, a, b);
+        else if constexpr (kOp == RRTE_SDF_SMOOTH_UNION) return smin(a, b, k);
+        else return -smin(-a, b, k);  // RRTE_SDF_SMOOTH_DIFFERENCE
     }
     __device__ __forceinline__ float operator()(f3 p) const {
-        GuardNow g;
-        return eval(p, g);
+        float a, b;
+        return eval_parts(p, a, b);
     }
 };
 
@@ -755,93 +709,6 @@ __device__ __forceinline__ bool leaves_sphere(float hb, float cc, float a, float
 // NaN anywhere fails both tests.  Shadow rays leaving the object they start on exit after ~3 steps
 // instead of marching out of the bound; camera and shadow rays that pass an object exit once they
 // recede from it.  (A miss's t is never used, so closest-hit marches take it too.)
-// Unroll factor of the sphere-tracing loops (RRTE_MARCH_UNROLL, A/B experiments through
-// RRTE_JIT_EXTRA_OPTS; the per-lane exit keeps every unrolled copy exact).
-#ifndef RRTE_MARCH_UNROLL
-#define RRTE_MARCH_UNROLL 1
-#endif
-// RRTE_MARCH_PRED (A/B switch, bit-exact at every level; tools/jit_ab.sh): 0 divergent-exit march loops
-// (default); 1 the predicated loop (sdf_march_loop) after the divergent bound test; 2 + a predicated
-// bound test (the loop runs under the caller's EXEC); 3 + predicated shadow rays (every lane of the
-// wave runs every any-hit test).  Measured on the headline (two interleaved rounds each): 1 = lone
-// launch -6 %, frame stream +1.5 %; 3 = frame stream +9 %, lone launch unchanged.
-#ifndef RRTE_MARCH_PRED
-#define RRTE_MARCH_PRED 0
-#endif
-#ifndef RRTE_MARCH_PAIR
-#define RRTE_MARCH_PAIR 0  // sphere-tracing loops exit every second step (A/B)
-#endif
-#define RRTE_PRAGMA_(x) _Pragma(#x)
-#define RRTE_UNROLL_(n) RRTE_PRAGMA_(unroll n)
-// One SDF evaluation with deferred guards: the short sequences for every lane, one wave-uniform test
-// of the folded range checks, and the compiler's full sequences only when some lane needs them.
-#ifndef RRTE_DEFER_GUARDS
-#define RRTE_DEFER_GUARDS 0
-#endif
-template <class EVAL>
-__device__ __forceinline__ float eval_deferred(const EVAL& eval, f3 p) {
-#if RRTE_DEFER_GUARDS
-    GuardDefer g;
-    float d = eval.eval(p, g);
-    const uint64_t bad = __builtin_amdgcn_ballot_w64(g.bad());
-    if (__builtin_expect(bad != 0ull, 0)) {
-        GuardSlow gs;
-        const float ds = eval.eval(p, gs);
-        d = mask_select(bad, d, ds);
-    }
-    return d;
-#else
-    return eval(p);
-#endif
-}
-
-// The predicated sphere-tracing loop (RRTE_MARCH_PRED): the lanes of `live` (an SGPR lane mask) march
-// from t to tend under the caller's EXEC; a lane that has stopped keeps its state through selects on
-// that mask, the step counter is wave-uniform (SGPR), and the loop ends when no lane is left -- the
-// same t sequence and result per lane as the divergent-exit loops of sdf_march, without their per-step
-// EXEC save / restore chains on the scalar unit.
-template <class EVAL, bool CONVEX>
-__device__ __forceinline__ bool sdf_march_loop(const DPrim& pr, const EVAL& eval, const Ray& r, float t, float tend,
-                                               uint64_t live, float& t_hit) {
-    const f3 bc = V(pr.p[0], pr.p[1], pr.p[2]);
-    const float br = pr.p[3];
-    const float eps = pr.sdf_hit_eps, scale = pr.sdf_step_scale;
-    const uint32_t steps = pr.sdf_max_steps;
-    [[maybe_unused]] float E = 0.0f, D3 = 0.0f, dp = __builtin_nanf(""), tp = t;
-    if constexpr (CONVEX) {
-        E = eps * (1.0f + 0x1p-20f);
-        const float K = eval.leaf_scale();
-        D3 = 3.0f * 0x1p-17f *
-             ((((fabsf(r.o.x) + fabsf(r.o.y)) + fabsf(r.o.z)) + tend) +
-              ((((fabsf(bc.x) + fabsf(bc.y)) + fabsf(bc.z)) + 4.0f * br) + K));
-    }
-    // every condition as a wave mask (one v_cmp each, combined on the scalar unit)
-    uint64_t hitm = 0ull;
-    uint32_t left = steps;
-    if (left != 0u) {
-        for (;;) {
-            const f3 p = ray_at(r, t);
-            const float d = eval_deferred(eval, p);
-            const float tn = t + d * scale;
-            const uint64_t hm = __builtin_amdgcn_ballot_w64(d < eps * t);
-            uint64_t sm = hm | __builtin_amdgcn_ballot_w64(tn > tend);
-            if constexpr (CONVEX) {
-                sm |= __builtin_amdgcn_ballot_w64(d - E * t >= D3) &
-                      __builtin_amdgcn_ballot_w64((d - dp) - E * (t - tp) >= D3);
-                dp = d;
-                tp = t;
-            }
-            hitm |= hm & live;
-            t = mask_select(live & ~hm, t, tn);
-            live &= ~sm;
-            left = __builtin_amdgcn_readfirstlane(left - 1u);
-            if ((left == 0u) | (live == 0ull)) break;
-        }
-    }
-    t_hit = t;
-    return mask_lane(hitm);
-}
-
 template <class EVAL, bool ANY = false, bool CONVEX = false>
 __device__ __forceinline__ bool sdf_march(const DPrim& pr, const EVAL& eval, const Ray& r, float t_min, float t_max,
                                           float& t_hit) {
@@ -850,25 +717,6 @@ __device__ __forceinline__ bool sdf_march(const DPrim& pr, const EVAL& eval, con
     f3 oc = vsub(r.o, bc);
     float b = vdot(oc, r.d);
     float cc = vdot(oc, oc) - br * br;
-#if RRTE_MARCH_PRED >= 2
-    // Predicated bound test: no divergent early return -- every lane of the caller's EXEC computes the
-    // entry and exit parameters, `enter` says whether it marches (the same decisions as the branches
-    // below), and the march loop runs under the caller's EXEC with the marching lanes in `live`.
-    // Lanes that do not enter get a benign t (their points stay finite, so no guard fallback runs).
-    {
-        const float disc = b * b - cc;
-        bool enter = !(disc < 0.0f);
-        if constexpr (ANY) enter = enter & !(t_max == t_max && leaves_sphere(b, cc, 1.0f, t_min));
-        const float sq = sqrt_rn(disc < 0.0f ? 1.0f : disc);
-        float t = mx(t_min, -b - sq);
-        const float tend = mn(t_max, -b + sq);
-        enter = enter & !(t > tend);
-        uint64_t live = __builtin_amdgcn_ballot_w64(enter);
-        if (live == 0ull) return false;
-        t = enter ? t : 1.0f;
-        return sdf_march_loop<EVAL, CONVEX>(pr, eval, r, t, tend, live, t_hit);
-    }
-#endif
     // the bound test below has no divide (roots -b -/+ sq): leaves_sphere's argument with a = 1, which
     // leaves tend = mn(t_max, -b + sq) <= 2^-60 < t_min <= t unless t_max is NaN (tend NaN marches on)
     if (ANY && t_max == t_max && leaves_sphere(b, cc, 1.0f, t_min)) return false;
@@ -880,15 +728,11 @@ __device__ __forceinline__ bool sdf_march(const DPrim& pr, const EVAL& eval, con
     if (t > tend) return false;
     const float eps = pr.sdf_hit_eps, scale = pr.sdf_step_scale;
     const uint32_t steps = pr.sdf_max_steps;
-#if RRTE_MARCH_PRED == 1
-    // the predicated loop under the EXEC of the lanes that passed the bound test
-    return sdf_march_loop<EVAL, CONVEX>(pr, eval, r, t, tend, __builtin_amdgcn_ballot_w64(true), t_hit);
-#endif
     // One divergent exit per step (hit, or the next t leaves the bound) instead of three: same
     // t sequence and result as "if (d < eps*t) hit; t += d*scale; if (t > tend) miss" (NaN
     // included).  (A fully predicated form with a wave-uniform exit was measured slower.)
     bool hit = false;
-    if constexpr (EVAL::kPlan >= 2 && RRTE_PARTS_EXIT && !RRTE_MARCH_PAIR && !RRTE_DEFER_GUARDS) {
+    if constexpr (EVAL::kPlan >= 2 && RRTE_PARTS_EXIT) {
         // part-wise secant early miss (SdfPartsProgram): every needed part proven to stay above
         // E t + margin by its own secant; D as below (the parts are leaves of the same program)
         const float E = eps * (1.0f + 0x1p-20f);
@@ -898,12 +742,11 @@ __device__ __forceinline__ bool sdf_march(const DPrim& pr, const EVAL& eval, con
         const float D3 = 3.0f * D;
         const float D3M = EVAL::kSmooth ? (D3 + D) + EVAL::kQuarterK : D3;
         float ap = __builtin_nanf(""), bp = __builtin_nanf(""), tp = t;
-RRTE_UNROLL_(RRTE_MARCH_UNROLL)
+#pragma unroll 1
         for (uint32_t i = 0; i < steps; ++i) {
             f3 p = ray_at(r, t);
-            GuardNow g;
             float a, b;
-            float d = eval.eval_parts(p, g, a, b);
+            float d = eval.eval_parts(p, a, b);
             hit = d < eps * t;
             const float tn = t + d * scale;
             bool safe = (a - E * t >= D3M) && ((a - ap) - E * (t - tp) >= D3);
@@ -925,34 +768,10 @@ RRTE_UNROLL_(RRTE_MARCH_UNROLL)
                          ((((fabsf(r.o.x) + fabsf(r.o.y)) + fabsf(r.o.z)) + tend) +
                           ((((fabsf(bc.x) + fabsf(bc.y)) + fabsf(bc.z)) + 4.0f * br) + K));
         float dp = __builtin_nanf(""), tp = t;
-#if RRTE_MARCH_PAIR
-        // two steps per loop exit (see below)
-        for (uint32_t i = 0; i < steps; i += 2u) {
-            const float dA = eval_deferred(eval, ray_at(r, t));
-            const bool hitA = dA < eps * t;
-            const float tnA = t + dA * scale;
-            const bool stopA = hitA || tnA > tend || ((dA - E * t >= D3) && ((dA - dp) - E * (t - tp) >= D3));
-            const float tA = hitA ? t : tnA;
-            if (i + 1u >= steps) {  // (uniform: an odd step cap ends on a single step)
-                hit = hitA;
-                t = tA;
-                break;
-            }
-            const float dB = eval_deferred(eval, ray_at(r, tA));
-            const bool hitB = dB < eps * tA;
-            const float tnB = tA + dB * scale;
-            const bool stopB = hitB || tnB > tend || ((dB - E * tA >= D3) && ((dB - dA) - E * (tA - t) >= D3));
-            hit = stopA ? hitA : hitB;
-            dp = stopA ? dA : dB;
-            tp = stopA ? t : tA;
-            t = stopA ? tA : (hitB ? tA : tnB);
-            if (stopA || stopB) break;
-        }
-#else
-RRTE_UNROLL_(RRTE_MARCH_UNROLL)
+#pragma unroll 1
         for (uint32_t i = 0; i < steps; ++i) {
             f3 p = ray_at(r, t);
-            float d = eval_deferred(eval, p);
+            float d = eval(p);
             hit = d < eps * t;
             const float tn = t + d * scale;
             const bool safe = (d - E * t >= D3) && ((d - dp) - E * (t - tp) >= D3);
@@ -962,40 +781,13 @@ RRTE_UNROLL_(RRTE_MARCH_UNROLL)
             t = hit ? t : tn;
             if (stop) break;
         }
-#endif
         t_hit = t;
         return hit;
     }
-#if RRTE_MARCH_PAIR
-    // Two march steps per loop exit: the second step runs on every lane that entered the iteration,
-    // and a lane whose first step stopped keeps that step's result through selects -- the same t
-    // sequence and result per lane as one exit per step, with half the divergent-exit bookkeeping on
-    // the scalar unit (a wave whose last lanes stop on a first step pays one extra step).
-    for (uint32_t i = 0; i < steps; i += 2u) {
-        const float dA = eval_deferred(eval, ray_at(r, t));
-        const bool hitA = dA < eps * t;
-        const float tnA = t + dA * scale;
-        const bool stopA = hitA || tnA > tend;
-        const float tA = hitA ? t : tnA;
-        if (i + 1u >= steps) {
-            hit = hitA;
-            t = tA;
-            break;
-        }
-        const float dB = eval_deferred(eval, ray_at(r, tA));
-        const bool hitB = dB < eps * tA;
-        const float tnB = tA + dB * scale;
-        hit = stopA ? hitA : hitB;
-        t = stopA ? tA : (hitB ? tA : tnB);
-        if (stopA || hitB || tnB > tend) break;
-    }
-    t_hit = t;
-    return hit;
-#endif
-RRTE_UNROLL_(RRTE_MARCH_UNROLL)
+#pragma unroll 1
     for (uint32_t i = 0; i < steps; ++i) {
         f3 p = ray_at(r, t);
-        float d = eval_deferred(eval, p);
+        float d = eval(p);
         hit = d < eps * t;
         const float tn = t + d * scale;
         const bool stop = hit || tn > tend;
@@ -1013,12 +805,12 @@ template <class EVAL>
 __device__ __forceinline__ void sdf_hit_attributes(const EVAL& eval, const Ray& r, float t, Hit& out) {
     const float h = 1e-3f;
     const f3 p = ray_at(r, t);
-    auto taps = [&](auto& g) {
+    auto taps = [&] {  // (a lambda of its own: written straight into this function the loop compiles differently)
         f3 n = V(0.0f, 0.0f, 0.0f);
         auto tap = [&](uint32_t k) {
             bool sx = (k == 0) || (k == 3), sy = (k >= 2), sz = (k == 1) || (k == 3);
             f3 q = V(sx ? p.x + h : p.x - h, sy ? p.y + h : p.y - h, sz ? p.z + h : p.z - h);
-            float d = eval.eval(q, g);
+            float d = eval(q);
             if (k == 0) { n.x = d; n.y = -d; n.z = -d; }
             else if (k == 1) { n.x = n.x - d; n.y = n.y - d; n.z = n.z + d; }
             else if (k == 2) { n.x = n.x - d; n.y = n.y + d; n.z = n.z - d; }
@@ -1035,20 +827,7 @@ __device__ __forceinline__ void sdf_hit_attributes(const EVAL& eval, const Ray& 
         }
         return n;
     };
-#if RRTE_DEFER_GUARDS
-    // deferred guards over the four taps: one wave-uniform test, the full sequences only if needed
-    GuardDefer g;
-    f3 n = taps(g);
-    const uint64_t bad = __builtin_amdgcn_ballot_w64(g.bad());
-    if (__builtin_expect(bad != 0ull, 0)) {
-        GuardSlow gs;
-        const f3 ns = taps(gs);
-        n = V(mask_select(bad, n.x, ns.x), mask_select(bad, n.y, ns.y), mask_select(bad, n.z, ns.z));
-    }
-#else
-    GuardNow g;
-    const f3 n = taps(g);
-#endif
+    const f3 n = taps();
     hit_new(out, t, p, vnorm(n), r);
 }
 
@@ -1058,7 +837,6 @@ __device__ __forceinline__ void local_ray(const DPrim& pr, const Ray& r, Ray& lr
     lr = ray_new(m_point(pr.inv, r.o), vnorm(m_vector(pr.inv, r.d)));
 }
 
-// ----------------------------------------------------- analytic intersectors
 // SceneObject::intersect for the seven primitive kinds (primitives.rs:57-725).
 // t is always written to out.t; point/normal only matter when NEED_HIT.
 template <bool NEED_HIT, bool ANY = false>
@@ -1345,14 +1123,9 @@ __device__ __forceinline__ bool mesh_tri_hit(const MeshView& mv, uint32_t k, con
 // Workgroup geometry: one wave per workgroup, one 8x8 pixel tile each (kBlockThreads = 64).  A
 // workgroup's waves must start together on one CU and a 4-wave workgroup needs a free slot on every
 // SIMD, so with a few long-running (grazing-ray) waves resident, 256-thread workgroups of 16x16 pixels
-// left slots idle that single waves fill: -9 % per frame.  RRTE_WG256 (defined by the
-// host for RRTE_WG64=0, an A/B switch for the specialised kernels) restores the 256-thread layout.
-#ifdef RRTE_WG256
-constexpr bool kWg64 = false;
-#else
-constexpr bool kWg64 = true;
-#endif
-constexpr uint32_t kBlockThreads = kWg64 ? 64u : 256u;
+// left slots idle that single waves fill: -9 % per frame (a switch that restored the
+// 256-thread layout for that A/B has been retired).
+constexpr uint32_t kBlockThreads = 64u;
 
 constexpr int kMeshStack = 32;  // BVH depth is capped below this at build time
 __device__ __forceinline__ uint32_t* mesh_stack() {
@@ -1550,10 +1323,10 @@ constexpr bool prim_convex() {
     else return sdf_convex(S::nodes + S::prims[I].sdf_first, S::prims[I].sdf_count);
 }
 // Part-wise secant plan of object I (sdf_parts_plan): full scenes only (a topology kernel keeps the
-// whole-program convexity its host computed), and only with the default march loops.
+// whole-program convexity its host computed).
 template <class S, uint32_t I>
 constexpr int prim_parts_plan() {
-    if constexpr (S::kTopo || !RRTE_PARTS_EXIT || RRTE_MARCH_PAIR || RRTE_MARCH_PRED != 0 || RRTE_DEFER_GUARDS)
+    if constexpr (S::kTopo || !RRTE_PARTS_EXIT)
         return 0;
     else if constexpr (S::prims[I].kind != RRTE_PRIM_SDF || S::prims[I].sdf_count != 3u)
         return 0;
@@ -1597,7 +1370,7 @@ __device__ __forceinline__ int closest_t(const S& sc, const Ray& r, float t_min,
     int idx = -1;
     best_t = kInf;
     best_sub = 0u;
-    for_each_prim_exp<1>(sc, [&](auto ii) {
+    for_each_prim(sc, [&](auto ii) {
         const uint32_t i = ii;
         if (i < 32u && !((pmask >> i) & 1u)) return;
         Hit h;
@@ -1724,23 +1497,13 @@ template <class S>
 __device__ __forceinline__ bool occluded(const S& sc, const Ray& r, float t_min, float t_max, uint64_t mask,
                                          int self = -1) {
     bool hit_any = false;
-    for_each_prim_exp<2>(sc, [&](auto ii) {
+    for_each_prim(sc, [&](auto ii) {
         const uint32_t i = ii;
         // one wave-uniform skip test: culled, or every lane already occluded (mask cleared)
         if (mask == 0 || (i < 64u && !((mask >> i) & 1ull))) return;
         Hit h;
-#if RRTE_MARCH_PRED >= 3
-        // predicated: every lane of the caller's EXEC runs the test (marches stay wide, see
-        // sdf_march_loop); lanes that are already occluded or that cast no ray (t_max = -inf) get an
-        // empty interval, for which every intersector reports no hit
-        const float tm = (hit_any || (int)i == self) ? -kInf : t_max;
-        const bool hi = any_hit_at(sc, ii, r, t_min, tm, h);
-        hit_any = hit_any | hi;
-        if (__all(hit_any | !(t_max != -kInf))) mask = 0;
-#else
         if (!hit_any && (int)i != self && any_hit_at(sc, ii, r, t_min, t_max, h)) hit_any = true;
         if (__all(hit_any)) mask = 0;
-#endif
     });
     return hit_any;
 }
@@ -2163,11 +1926,6 @@ __device__ __forceinline__ Col ray_color_ref(const S& sc, const KParams& kp, Ray
     return ps.out;
 }
 
-// LAMBERT_SHADOW (build-defined, DESIGN.md §6) for one camera ray.  Called by
-// all 64 lanes of the wave (`live` marks the lanes that own a pixel): with
-// CULL the hit-point bound and the per-light shadow culls are wave reductions.
-constexpr bool kShadeAll = RRTE_MARCH_PRED >= 3;  // shade every lane (predicated), or only hit lanes
-
 // Launch traits of ray_kernel_body: what the kernel may assume about its launch at compile time.
 // LaunchAny assumes nothing.  LaunchPlain is the frame an engine renders in a stream (the host checks
 // every condition before it picks that entry, rrte_hip.hip plain_launch): one frame per launch
@@ -2186,6 +1944,9 @@ __device__ __forceinline__ uint32_t launch_debug(const KParams& kp) {
     else return kp.debug;
 }
 
+// LAMBERT_SHADOW (build-defined, DESIGN.md §6) for one camera ray.  Called by
+// all 64 lanes of the wave (`live` marks the lanes that own a pixel): with
+// CULL the hit-point bound and the per-light shadow culls are wave reductions.
 template <class S, bool CULL, class LT = LaunchAny>
 __device__ __forceinline__ Col shade_lambert(const S& sc, const KParams& kp, const Cull& cl, const Ray& r, bool live,
                                              uint32_t& nshadow, uint32_t pmask) {
@@ -2193,7 +1954,7 @@ __device__ __forceinline__ Col shade_lambert(const S& sc, const KParams& kp, con
     Col out{0.0f, 0.0f, 0.0f, 1.0f};
     if (kp.max_depth == 0) return out;
     Hit h;
-    h.t = 0.0f;  // lanes without a hit keep a benign point and normal (predicated shading, RRTE_MARCH_PRED)
+    h.t = 0.0f;  // lanes without a hit keep a benign point and normal
     h.p = V(0.0f, 0.0f, 0.0f);
     h.n = V(0.0f, 1.0f, 0.0f);
     h.front = true;
@@ -2230,26 +1991,7 @@ __device__ __forceinline__ Col shade_lambert(const S& sc, const KParams& kp, con
             return;
         }
         const float ndl = vdot(h.n, k.dir);
-#if RRTE_MARCH_PRED >= 3
-        // predicated over every lane (hit or not): a lane that casts no shadow ray tests the empty
-        // interval (t_max = -inf) along a benign direction, so the any-hit marches run wide
-        const bool cast = hit && ndl > 0.0f && k.att > 0.0f;
-        nshadow += cast ? 1u : 0u;
-        {
-            const Ray sr = ray_new_unit(vadd(h.p, vmuls(h.n, bias)), cast ? k.dir : V(0.0f, 1.0f, 0.0f));
-            const bool skip = (debug & 1u) || ((debug & 256u) && li != ((debug >> 9) & 7u));
-            const bool occ = !skip && occluded(sc, sr, bias, cast ? k.dist : -kInf, smask, (debug & 64u) ? idx : -1);
-            if (cast && !occ) {
-                float f = k.att * ndl;
-                cr = cr + ar * (k.cr * f);
-                cg = cg + ag * (k.cg * f);
-                cb = cb + ab * (k.cb * f);
-            }
-        }
-        if (false) {
-#else
         if (ndl > 0.0f && k.att > 0.0f) {
-#endif
             ++nshadow;
             Ray sr = ray_new_unit(vadd(h.p, vmuls(h.n, bias)), k.dir);
             // RRTE_DEBUG bit 6 (timing diagnostics only, wrong images): skip the object the ray starts on
@@ -2263,7 +2005,7 @@ __device__ __forceinline__ Col shade_lambert(const S& sc, const KParams& kp, con
         }
     };
     if constexpr (!CULL) {
-        if (kShadeAll || hit) for_each_light(sc, [&](auto lii) { shade(light_at(sc, lii), ~0ull, (uint32_t)lii); });
+        if (hit) for_each_light(sc, [&](auto lii) { shade(light_at(sc, lii), ~0ull, (uint32_t)lii); });
     } else {
         HitBound hb{};
         hb.unsafe = true;  // no bounds table: every mask all-ones
@@ -2278,7 +2020,7 @@ __device__ __forceinline__ Col shade_lambert(const S& sc, const KParams& kp, con
                 auto cull_one = [&](auto lii) { smask[(uint32_t)lii] = shadow_cull(cl, hb, light_at(sc, lii), bnd); };
                 static_for<0, S::num_lights>(cull_one);
             }
-            auto shade_one = [&](auto lii) { if (kShadeAll || hit) shade(light_at(sc, lii), smask[(uint32_t)lii], (uint32_t)lii); };
+            auto shade_one = [&](auto lii) { if (hit) shade(light_at(sc, lii), smask[(uint32_t)lii], (uint32_t)lii); };
             static_for<0, S::num_lights>(shade_one);
         } else {
             const float4 bnd = cull_on(cl) ? load_bound(cl) : float4{};
@@ -2286,7 +2028,7 @@ __device__ __forceinline__ Col shade_lambert(const S& sc, const KParams& kp, con
             for (uint32_t li = 0; li < sc.num_lights; ++li) {
                 const DLight lt = load_uniform(sc.lights + li);  // (li uniform: scalar loads)
                 const uint64_t sm = shadow_cull(cl, hb, lt, bnd);
-                if (kShadeAll || hit) shade(lt, sm, li);
+                if (hit) shade(lt, sm, li);
             }
         }
     }
@@ -2363,19 +2105,11 @@ __device__ __forceinline__ uint32_t camera_tile_mask(const KParams& kp, const Fr
                                                      uint32_t ty) {
     const uint32_t sh = cm.tile_cull;
     if (!sh) return ~0u;
-    uint32_t bx, bx1, by;
-    if (kWg64) {  // one tile per workgroup: (1 << tile_shift) x (64 >> tile_shift) pixels
-        // (its rows lie in one 8-row block of consecutive image rows: 64 >> tile_shift divides 8 and
-        // band heights are multiples of 8)
-        bx = (tx << kp.tile_shift) >> sh;
-        bx1 = ((tx << kp.tile_shift) + (1u << kp.tile_shift) - 1u) >> sh;
-        by = image_row<LT>(kp, ty * (64u >> kp.tile_shift)) >> sh;
-    } else {
-        const uint32_t wave = sh == 3u ? (threadIdx.x >> 6) : 0u;
-        bx = (blockIdx.x * 16u + (wave & 1u) * 8u) >> sh;
-        bx1 = bx;
-        by = image_row<LT>(kp, blockIdx.y * 16u + (wave >> 1) * 8u) >> sh;
-    }
+    // one tile per workgroup: (1 << tile_shift) x (64 >> tile_shift) pixels (its rows lie in one 8-row
+    // block of consecutive image rows: 64 >> tile_shift divides 8 and band heights are multiples of 8)
+    const uint32_t bx = (tx << kp.tile_shift) >> sh;
+    const uint32_t bx1 = ((tx << kp.tile_shift) + (1u << kp.tile_shift) - 1u) >> sh;
+    const uint32_t by = image_row<LT>(kp, ty * (64u >> kp.tile_shift)) >> sh;
     const uint32_t j = threadIdx.x & 63u;
     bool in = false;
     if (j < cm.tile_n) {  // the rectangle meets the tile's blocks [bx, bx1] x by
@@ -2391,7 +2125,6 @@ __device__ __forceinline__ uint32_t camera_tile_mask(const KParams& kp, const Fr
 // index: one scalar load); run = false for the unused slots of the last slot row.
 struct LaunchTile { uint32_t x, y, z; bool run; };
 __device__ __forceinline__ LaunchTile launch_tile(const KParams& kp) {
-    if (!kWg64) return LaunchTile{blockIdx.x, blockIdx.y, blockIdx.z, true};
     LaunchTile t{blockIdx.x, blockIdx.z, blockIdx.y, true};
     if (kp.hot) {
         const uint32_t k = blockIdx.z * kp.tiles_x + blockIdx.x;
@@ -2428,7 +2161,7 @@ __device__ __forceinline__ bool launch_indices_ok(const KParams& kp, unsigned lo
     return bad == 0u;
 }
 
-// One lane per pixel; wave = workgroup = 8x8 tile (RRTE_WG256: 16x16-pixel workgroups).  Every lane
+// One lane per pixel; wave = workgroup = 8x8 tile.  Every lane
 // of a wave runs the sample loop (lanes past the image edge are idle but
 // present) so the culling reductions see converged waves.  CULL selects the
 // shadow-culled LAMBERT_SHADOW variant (the host picks it per scene).
@@ -2440,11 +2173,11 @@ __device__ __forceinline__ void ray_kernel_body(const KParams& kp, const S& sc, 
     constexpr bool kPlain = LT::kPlain;
     static_assert(!kPlain || SINGLE, "a plain launch renders one sample per pixel");
     const uint32_t debug = launch_debug<LT>(kp);
-    const uint32_t lane = threadIdx.x & 63u, wave = kWg64 ? 0u : threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
     // RRTE_DEBUG bit 2 (diagnostics): every index this wave derives from the launch (list slot, tile,
     // frame) is range-checked before use; a violation sets a bit in the check word (counters[1], an
     // unused word of shard 0; rrte_hip_check_word) and the wave stops instead of touching memory
-    if ((debug & 4u) && kWg64 && !launch_indices_ok(kp, counters)) return;
+    if ((debug & 4u) && !launch_indices_ok(kp, counters)) return;
     LaunchTile tile = launch_tile(kp);
     if (!tile.run) return;
     if constexpr (kPlain) tile.z = 0u;
@@ -2459,15 +2192,15 @@ __device__ __forceinline__ void ray_kernel_body(const KParams& kp, const S& sc, 
     // RRTE_DEBUG bit 4 (diagnostics, tools/wave_times.py): per-wave start / duration from the 100 MHz
     // wall clock into the f32 buffer instead of colours
     const bool stamps = !kPlain && (debug & 16u) && out_f32;
-    const uint32_t tiles_x = kWg64 ? kp.tiles_x : gridDim.x;
+    const uint32_t tiles_x = kp.tiles_x;
     // bit 5: only workgroup (debug >> 16) runs (its waves' durations alone on the GPU)
     const uint32_t brow = tile.y;
     if ((debug & 32u) && brow * tiles_x + tile.x != (debug >> 16)) return;
     const bool timed = stamps || (kp.tile_cost && tile.z == 0u);
     const uint64_t t_wave0 = timed ? wall_clock64() : 0ull;
-    const uint32_t ts = kp.tile_shift;  // (kWg64: tile 1 << ts wide, 64 >> ts rows)
-    const uint32_t x = kWg64 ? (tile.x << ts) + (lane & ((1u << ts) - 1u)) : tile.x * 16u + (wave & 1u) * 8u + (lane & 7u);
-    const uint32_t lr = kWg64 ? brow * (64u >> ts) + (lane >> ts) : brow * 16u + (wave >> 1) * 8u + (lane >> 3);
+    const uint32_t ts = kp.tile_shift;  // (tile 1 << ts wide, 64 >> ts rows)
+    const uint32_t x = (tile.x << ts) + (lane & ((1u << ts) - 1u));
+    const uint32_t lr = brow * (64u >> ts) + (lane >> ts);
     bool live = x < kp.width && lr < kp.rows;
     const uint32_t xc = live ? x : 0u;
     const uint32_t y = image_row<LT>(kp, live ? lr : 0u);
@@ -2610,11 +2343,11 @@ __device__ __forceinline__ void ray_kernel_body(const KParams& kp, const S& sc, 
             atomicAdd(counters + shard * kCounterStride, (unsigned long long)v);
         }
     }
-    if (kWg64 && kp.tile_cost && tile.z == 0u && lane == 0)  // tile profile (TileProfile, rrte_hip.hip)
+    if (kp.tile_cost && tile.z == 0u && lane == 0)  // tile profile (TileProfile, rrte_hip.hip)
         kp.tile_cost[brow * tiles_x + tile.x] = (uint32_t)(wall_clock64() - t_wave0);
     if (stamps && lane == 0) {
         const uint64_t t1 = wall_clock64();
-        const uint32_t wid = (brow * tiles_x + tile.x) * 4u + wave;
+        const uint32_t wid = (brow * tiles_x + tile.x) * 4u;  // (every fourth record: tools/wave_times.py)
         uint32_t* s = reinterpret_cast<uint32_t*>(out_f32) + 4u * wid;
         s[0] = (uint32_t)t_wave0;
         s[1] = (uint32_t)(t_wave0 >> 32);

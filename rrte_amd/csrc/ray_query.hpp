@@ -9,8 +9,8 @@
 // interval in place of [kp.t_min, +inf), so a query is bit-identical to a loop over
 // SceneObject::intersect (raytracer.rs:103-113).
 //
-// Tail and finished lanes: the search contains wave-wide operations (the ballot exits of
-// sdf_march_loop, readfirstlane in the attribute walk, __all in the any-hit loop), so a lane past
+// Tail and finished lanes: the search contains wave-wide operations (the __all of the CSG guards in
+// sdf_guard, readfirstlane in the attribute walk, __all in the any-hit loop), so a lane past
 // `n` -- and an any-hit lane that has its answer -- never returns early.  It stays in the wave with
 // a benign ray and the empty interval [+inf, -inf], for which every intersector reports no hit, and
 // it neither loads a ray nor stores a hit.

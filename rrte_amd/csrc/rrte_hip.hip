@@ -227,7 +227,6 @@ struct rrte_ctx {
                                     // through RCCL and expands them like a peer's (the 1-GPU check of the
                                     // send / recv / expand path)
     uint32_t env_guard_leaves = 2;  // RRTE_CSG_GUARDS: 0 = off, N = smallest guarded operand (leaves)
-    bool env_wg256 = false;           // RRTE_WG64=0: specialised kernels in 256-thread workgroups (A/B only)
     int emu_nranks = 0, emu_rank = 0;  // RRTE_EMULATE_RANK=N:R: render_async renders rank R's bands of N (diagnostic)
     // RRTE_EMULATE_PEERS=N (tests, one GPU): a 1-rank communicator acts as the root of N ranks, and the
     // root renders every peer's packed share (exactly what RRTE_EMULATE_RANK=N:q renders, RGB24 slab
@@ -1515,7 +1514,6 @@ JitKernel* jit_lookup(rrte_ctx* c, const std::string& key, bool topo, int mode, 
                                      (uint32_t)c->h_mats.size(), c->h_lights.data(), (uint32_t)c->h_lights.size(),
                                      c->h_nodes.data(), (uint32_t)c->h_nodes.size(), mode, cull, single,
                                      topo ? &c->topo : nullptr);
-        if (c->env_wg256) src = "#define RRTE_WG256 1\n" + src;
         if (uniform) src = "#define RRTE_GUARD_UNIFORM 1\n" + src;
         if (c->jit_mode == RRTE_JIT_AUTO) {
             // compile on a background thread (hiprtc only); frames keep running on the current kernel
@@ -1773,7 +1771,7 @@ bool plan_tile_order(rrte_ctx* c, LaunchPlan& L, const void* kern, hipStream_t s
     k.tile_cost = nullptr;
     // (RRTE_DEBUG bit 5 runs one workgroup in image-order numbering: no tile order; bit 4's per-wave
     // stamps work with it)
-    if (!c->env_tile_order || c->env_wg256 || L.gx > 0xffffu || L.gy > 0xffffu || (k.debug & 32u)) return false;
+    if (!c->env_tile_order || L.gx > 0xffffu || L.gy > 0xffffu || (k.debug & 32u)) return false;
     auto& tp = c->tprof[L.prof];
     std::string key(reinterpret_cast<const char*>(&kern), sizeof kern);
     const uint32_t shape[] = {k.width, k.height, k.rows, k.row0, k.band_rows, k.nranks, k.rank, k.spp, k.max_depth,
@@ -1891,14 +1889,14 @@ void launch_generic(uint32_t need, dim3 grid, dim3 block, hipStream_t st, const 
 
 // Whether a launch of the specialised kernel `jk` meets every assumption of its plain entry
 // (ray_kernels.hpp LaunchPlain): one frame into the RGBA8 device buffer `d_rgba` alone, rows packed from
-// image row 0 with no band map, no debug bit, gamma 2.2, one sample per pixel (SINGLE kernels only
-// have the entry) and 64-thread workgroups.  Gather slabs, rank shares, multi-frame batches, f32
+// image row 0 with no band map, no debug bit, gamma 2.2 and one sample per pixel (SINGLE kernels only
+// have the entry).  Gather slabs, rank shares, multi-frame batches, f32
 // frames, zero-copy frames (rrte_ctx::host_out), RRTE_DEBUG and other gammas
 // fail one of the tests and take the general entry; RRTE_JIT_PLAIN=0 sends everything there.
 bool plain_launch(const rrte_ctx* c, const JitKernel* jk, const LaunchPlan& L, const uint32_t* d_rgba,
                   const float4* d_f32) {
     const KParams& k = L.k;
-    return c->env_jit_plain && jk->fn_plain && L.single && !c->env_wg256 && d_rgba && !d_f32 && !c->host_out &&
+    return c->env_jit_plain && jk->fn_plain && L.single && d_rgba && !d_f32 && !c->host_out &&
            k.nframes == 1 && k.band_rows == 0 && k.row0 == 0 && k.out_image_rows == 0 && k.debug == 0 &&
            !(k.flags & (kFlagSlabRgb24 | kFlagHostStore)) && k.inv_gamma == kInvGamma22 && k.inv_spp == 1.0f;
 }
@@ -1940,9 +1938,6 @@ rrte_status issue_launch(rrte_ctx* c, LaunchPlan& L, uint32_t* d_rgba, float4* d
         c->last_entry = plain ? RRTE_ENTRY_PLAIN : RRTE_ENTRY_GENERAL;
         if (plain)
             HIPCHK(c, hipModuleLaunchKernel(jk->fn_plain, grid.x, grid.y, grid.z, kBlockThreads, 1, 1, 0, st, args, nullptr));
-        else if (c->env_wg256)
-            HIPCHK(c, hipModuleLaunchKernel(jk->fn, (L.k.width + 15) / 16, (L.k.rows + 15) / 16, L.k.nframes, 256, 1, 1,
-                                            0, st, args, nullptr));
         else
             HIPCHK(c, hipModuleLaunchKernel(jk->fn, grid.x, grid.y, grid.z, kBlockThreads, 1, 1, 0, st, args, nullptr));
         hs.lap(c->hpa_cur ? 14 : 8);
@@ -2223,7 +2218,6 @@ rrte_status rrte_hip_create(int device, rrte_ctx** out) {
     if (const char* g = getenv("RRTE_GATHER_SELF")) c->env_gather_self = g[0] == '1';
     if (const char* g = getenv("RRTE_BAND_SKY")) c->env_band_sky = g[0] != '0';
     if (const char* g = getenv("RRTE_COMM_PRIORITY")) c->env_comm_priority = g[0] != '0';
-    if (const char* g = getenv("RRTE_WG64")) c->env_wg256 = g[0] == '0';
     if (const char* g = getenv("RRTE_GENERIC_ALL")) c->env_generic_all = g[0] == '1';
     if (const char* g = getenv("RRTE_GUARD_POLICY"); g && *g) c->env_guard_policy = std::min(2, std::max(0, atoi(g)));
     if (const char* g = getenv("RRTE_BATCH_LAUNCH")) c->env_batch_launch = g[0] != '0';

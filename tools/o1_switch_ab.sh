@@ -1,6 +1,6 @@
 set -o pipefail
 for k in 1 2; do
-  for v in "base||" "pair|-DRRTE_MARCH_PAIR=1|" "uniform||1"; do
+  for v in "base||" "uniform||1"; do
     name=${v%%|*}; rest=${v#*|}; opts=${rest%%|*}; gp=${rest#*|}
     for steps in 200 20; do
       RRTE_JIT_EXTRA_OPTS="$opts" RRTE_GUARD_POLICY=${gp:-0} timeout -k 10 200 python bench.py --full --no-cpu --no-boundary --no-stock --steps $steps > /tmp/ab3.json || exit 1
