@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../rrte_hip.h"
+#include "../rrte_hip_build.h"
 #include "../rrte_hip_query.h"
 #include "../rrte_hip_refit.h"
 
@@ -407,6 +408,10 @@ public:
     std::vector<uint8_t> render_deformed(const Objects& objects, const Lights& lights, const Materials& materials,
                                          const Camera& camera);
     rrte_refit_info refit_info() const;
+    // Who builds the BVH of a new mesh or a changed topology (include/rrte_hip_build.h):
+    // RRTE_MESH_BUILD_HOST (default) or RRTE_MESH_BUILD_DEVICE.  Takes effect at the next build.
+    void set_mesh_build(uint32_t policy);
+    rrte_build_info build_info() const;
     // Engine::render_frame's loop (engine.rs:82,293; rust/patches/0002): the frame into the caller's
     // buffer, reused every frame and pinned once (rrte_hip_host_register) so the kernel stores the
     // frame straight into it.  `out` is resized to W*H*4; a buffer that moved since it was pinned is

@@ -213,6 +213,23 @@ REFIT_EXPORTS = {
     "rrte_hip_mesh_slots": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]),
 }
 
+# ------------------------------------------------ the mesh build policy (include/rrte_hip_build.h)
+MESH_BUILD_HOST, MESH_BUILD_DEVICE = 0, 1
+
+
+class BuildInfo(C.Structure):
+    _fields_ = [("device_builds", C.c_uint64), ("host_fallbacks", C.c_uint64), ("policy", C.c_uint32),
+                ("depth", C.c_uint32)]
+
+
+assert C.sizeof(BuildInfo) == 24
+
+# Every entry point include/rrte_hip_build.h declares.
+BUILD_EXPORTS = {
+    "rrte_hip_set_mesh_build": (C.c_int, [_P, C.c_uint32]),
+    "rrte_hip_build_info": (C.c_int, [_P, C.POINTER(BuildInfo)]),
+}
+
 # ------------------------------------------------ specialised-kernel diagnostics (include/rrte_hip_jit.h)
 ENTRY_NONE, ENTRY_GENERIC, ENTRY_GENERAL, ENTRY_PLAIN = 0, 1, 2, 3
 
@@ -243,7 +260,8 @@ def load() -> C.CDLL:
     except Exception:
         pass
     lib = C.CDLL(str(LIB_PATH), mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**EXPORTS, **QUERY_EXPORTS, **MESH_EXPORTS, **REFIT_EXPORTS, **JIT_EXPORTS}.items():
+    for name, (res, args) in {**EXPORTS, **QUERY_EXPORTS, **MESH_EXPORTS, **REFIT_EXPORTS, **BUILD_EXPORTS,
+                               **JIT_EXPORTS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

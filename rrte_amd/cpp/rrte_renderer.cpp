@@ -660,6 +660,12 @@ rrte_refit_info Raytracer::refit_info() const {
     check(rrte_hip_refit_info(ctx_, &r));
     return r;
 }
+void Raytracer::set_mesh_build(uint32_t policy) { check(rrte_hip_set_mesh_build(ctx_, policy)); }
+rrte_build_info Raytracer::build_info() const {
+    rrte_build_info b;
+    check(rrte_hip_build_info(ctx_, &b));
+    return b;
+}
 void Raytracer::render_into(const Objects& objects, const Lights& lights, const Materials& materials,
                             const Camera& camera, std::vector<uint8_t>& out) {
     (void)materials;

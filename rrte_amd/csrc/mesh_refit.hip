@@ -198,22 +198,26 @@ void refit_range_bounds(const rrte_scene_ir* s, MeshData& md) {
     }
 }
 
-hipError_t launch_refit(const RefitStatic& rs, const RefitDevice& d, hipStream_t st) {
-    const uint32_t n_leaves = (uint32_t)rs.leaves.size();
+hipError_t launch_refit_levels(uint32_t n_leaves, const uint32_t* level_off, uint32_t levels, const RefitDevice& d,
+                               hipStream_t st) {
     if (n_leaves) {
         hipLaunchKernelGGL(refit_leaves, dim3((n_leaves + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, d,
                            n_leaves);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    for (uint32_t l = 0; l < rs.levels(); ++l) {
-        const uint32_t begin = rs.level_off[l], count = rs.level_off[l + 1] - begin;
+    for (uint32_t l = 0; l < levels; ++l) {
+        const uint32_t begin = level_off[l], count = level_off[l + 1] - begin;
         hipLaunchKernelGGL(refit_level, dim3((count + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, d, begin,
                            count);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_refit(const RefitStatic& rs, const RefitDevice& d, hipStream_t st) {
+    return launch_refit_levels((uint32_t)rs.leaves.size(), rs.level_off.data(), rs.levels(), d, st);
 }
 
 }  // namespace rrte

@@ -52,4 +52,9 @@ struct RefitDevice {
 // refit_leaves, then refit_level once per level, on `st`.
 hipError_t launch_refit(const RefitStatic& rs, const RefitDevice& d, hipStream_t st);
 
+// The same launches from counts alone (level l = d.order[level_off[l], level_off[l + 1])): for a
+// caller whose leaves and order tables exist only on the device (mesh_build.hip).
+hipError_t launch_refit_levels(uint32_t n_leaves, const uint32_t* level_off, uint32_t levels, const RefitDevice& d,
+                               hipStream_t st);
+
 }  // namespace rrte

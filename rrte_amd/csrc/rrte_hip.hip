@@ -29,10 +29,12 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../include/rrte_hip_build.h"
 #include "../../include/rrte_hip_jit.h"
 #include "../../include/rrte_hip_mesh.h"
 #include "../../include/rrte_hip_refit.h"
 #include "bvh.hpp"
+#include "mesh_build.hpp"
 #include "mesh_refit.hpp"
 #include "jit.hpp"
 #include "sdf_guard.hpp"
@@ -253,6 +255,16 @@ struct rrte_ctx {
     RefitStatic refit_static;         // of mesh_cache's topology (first refit after a build)
     bool refit_static_valid = false;
     uint64_t refits = 0, device_refits = 0;
+    // The mesh build policy (include/rrte_hip_build.h): who builds on a mesh-cache miss.
+    // The device builder's scratch is grown with ensure(), used on the upload stream only and waited
+    // for before build_meshes_device returns.
+    uint32_t mesh_build = RRTE_MESH_BUILD_HOST;
+    uint64_t device_builds = 0, host_fallbacks = 0;
+    uint32_t build_depth = 0;
+    DeviceBuilder builder;
+    uint8_t* d_build = nullptr;
+    size_t cap_build = 0;
+    BuildTimes build_times;  // (RRTE_HOST_PROFILE)
     bool env_generic_all = false;    // RRTE_GENERIC_ALL=1: the all-features generic kernel for every scene (A/B, tests)
     // Batched gathers render the batch's frames in multi-frame launches at its close (default), or with
     // RRTE_BATCH_LAUNCH=0 each frame at its call (its own launch on the caller's stream: the root in
@@ -908,6 +920,31 @@ void set_mesh_cache_key(rrte_ctx* c, const SceneKeyParts& kp) {
                                  static_cast<const unsigned char*>(kp.parts[i]) + kp.lens[i]);
 }
 
+// Policy DEVICE on a mesh-cache miss: the LBVH build (mesh_build.hip) on the upload stream into
+// `built`.  *done = false when the host builder must take this miss (counted by the caller).
+rrte_status build_meshes_device(rrte_ctx* c, const rrte_scene_ir* s, MeshData& built, bool* done) {
+    *done = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool planned = c->builder.plan(s);
+    if (c->host_prof)  // (a refused plan has paid for its scan too)
+        c->build_times.host_scan += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    if (!planned) return RRTE_OK;
+    rrte_status r;
+    if ((r = ensure(c, c->d_build, c->cap_build, c->builder.scratch_bytes())) != RRTE_OK) return r;
+    uint32_t depth = 0;
+    hipError_t err = hipSuccess;
+    const BuildResult br = c->builder.run(s, c->d_build, c->upload_stream, (c->env_debug & 4u) ? c->d_counters + 1 : nullptr,
+                                          built, &depth, &err, c->host_prof ? &c->build_times : nullptr);
+    if (br == BuildResult::HipError) HIPCHK(c, err);
+    if (br != BuildResult::Built) {
+        built = MeshData{};
+        return RRTE_OK;
+    }
+    c->build_depth = depth;
+    *done = true;
+    return RRTE_OK;
+}
+
 rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, double* upload_ms) {
     const size_t bn = sizeof(rrte_sdf_node) * s->num_sdf_nodes;
     SceneKeyParts kparts;
@@ -950,7 +987,14 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
     // scene version as it is (moving an instance, or anything else in the scene, builds no BVH)
     if (!mesh_cache_hit(c, kparts, s)) {
         MeshData built;
-        build_mesh_ranges(s, built);
+        bool on_device = false;
+        if (c->mesh_build == RRTE_MESH_BUILD_DEVICE) {
+            rrte_status br = build_meshes_device(c, s, built, &on_device);
+            if (br != RRTE_OK) return br;
+            if (on_device) c->device_builds += built.ranges.size();
+            else ++c->host_fallbacks;
+        }
+        if (!on_device) build_mesh_ranges(s, built);
         if (built.too_deep) return fail(c, RRTE_UNSUPPORTED_PRIM, "mesh BVH deeper than the traversal stack");
         c->bvh_builds += built.ranges.size();
         c->mesh_cache = std::move(built);
@@ -2207,6 +2251,10 @@ rrte_status rrte_hip_create(int device, rrte_ctx** out) {
     if (const char* t = getenv("RRTE_JIT_PLAIN")) c->env_jit_plain = t[0] != '0';
     if (const char* g = getenv("RRTE_FORCE_GATHER")) c->env_force_gather = g[0] == '1';
     if (const char* g = getenv("RRTE_HOST_PROFILE")) c->host_prof = g[0] == '1';
+    if (const char* g = getenv("RRTE_MESH_BUILD")) {
+        if (!strcmp(g, "device")) c->mesh_build = RRTE_MESH_BUILD_DEVICE;
+        else if (!strcmp(g, "host")) c->mesh_build = RRTE_MESH_BUILD_HOST;
+    }
     if (const char* g = getenv("RRTE_TRACE")) c->trace = g[0] == '1';
     if (const char* g = getenv("RRTE_DIAG_SKIP")) c->env_diag_skip = (uint32_t)strtoul(g, nullptr, 0);
     if (const char* g = getenv("RRTE_GATHER_RGB24")) c->env_gather_rgba = g[0] == '0';
@@ -2325,6 +2373,13 @@ void rrte_hip_destroy(rrte_ctx* c) {
         for (int i = 0; i < 9; ++i) fprintf(stderr, " %s %.2f", names[i], c->hpu[i] / (double)c->hpu_n);
         fprintf(stderr, "\n");
     }
+    if (c->host_prof && c->build_times.n) {
+        const BuildTimes& bt = c->build_times;
+        const double n = (double)bt.n;
+        fprintf(stderr, "rrte host profile (%llu device mesh builds, us/build): host_scan %.2f enqueue %.2f depth_wait %.2f "
+                        "boxes_enqueue %.2f readback %.2f\n",
+                (unsigned long long)bt.n, bt.host_scan / n, bt.enqueue / n, bt.depth_wait / n, bt.boxes_enqueue / n, bt.readback / n);
+    }
     if (c->trace) {
         for (const auto& t : c->trace_log)
             fprintf(stderr, "rrte trace %12.1f us  %-34s stream %p event %p  %u %u\n", t.us, t.what, t.st, t.ev, t.a, t.b);
@@ -2345,7 +2400,7 @@ void rrte_hip_destroy(rrte_ctx* c) {
         if (B.ev_up) (void)hipEventDestroy(B.ev_up);
         destroy_events(B.ret);
     }
-    void* bufs[] = {c->d_rgba, c->d_f32, c->d_counters, c->d_gather, c->d_full, c->d_qin, c->d_qout};
+    void* bufs[] = {c->d_rgba, c->d_f32, c->d_counters, c->d_gather, c->d_full, c->d_qin, c->d_qout, c->d_build};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (void* b : c->graveyard)
@@ -2502,6 +2557,24 @@ rrte_status rrte_hip_mesh_info(rrte_ctx* c, rrte_mesh_info* out) {
         out->tri_slots = (uint32_t)(c->mesh_cache.tris.size() / 3);
         out->bvh_nodes = (uint32_t)(c->mesh_cache.nodes.size() / 4);
     }
+    return RRTE_OK;
+}
+
+// include/rrte_hip_build.h
+rrte_status rrte_hip_set_mesh_build(rrte_ctx* c, uint32_t policy) {
+    if (!c) return RRTE_INVALID_ARG;
+    if (policy != RRTE_MESH_BUILD_HOST && policy != RRTE_MESH_BUILD_DEVICE)
+        return fail(c, RRTE_INVALID_ARG, "mesh build policy %u (0 host, 1 device)", policy);
+    c->mesh_build = policy;
+    return RRTE_OK;
+}
+
+rrte_status rrte_hip_build_info(rrte_ctx* c, rrte_build_info* out) {
+    if (!c || !out) return RRTE_INVALID_ARG;
+    out->device_builds = c->device_builds;
+    out->host_fallbacks = c->host_fallbacks;
+    out->policy = c->mesh_build;
+    out->depth = c->build_depth;
     return RRTE_OK;
 }
 

@@ -883,6 +883,19 @@ class Context:
         self.check(self.lib.rrte_hip_refit_info(self.h, C.byref(r)))
         return r
 
+    def set_mesh_build(self, policy: int) -> None:
+        """rrte_hip_set_mesh_build (include/rrte_hip_build.h): who builds the BVHs at the next mesh-cache
+        miss, abi.MESH_BUILD_HOST (binned SAH on the host) or abi.MESH_BUILD_DEVICE (LBVH kernels).
+        Host only; rebuilds nothing by itself."""
+        self.check(self.lib.rrte_hip_set_mesh_build(self.h, int(policy)))
+
+    def build_info(self) -> abi.BuildInfo:
+        """rrte_hip_build_info: ranges built on the device, cache misses under policy DEVICE the host
+        built after all, the policy, and the depth (records on a path) of the last device build."""
+        b = abi.BuildInfo()
+        self.check(self.lib.rrte_hip_build_info(self.h, C.byref(b)))
+        return b
+
     def mesh_nodes(self) -> np.ndarray:
         """rrte_hip_mesh_nodes: the current scene version's BVH interior records as a (records, 4, 4)
         float32 array (child 0 lo + link, hi + axis, child 1 lo + link, hi); view it as uint32 for
@@ -918,11 +931,14 @@ class Context:
 class Raytracer:
     """Raytracer (raytracer.rs:28-149), rendering on an MI355X."""
 
-    def __init__(self, config: RaytracerConfig | None = None, device: int | None = None, jit: int | None = None):
-        """jit: abi.JIT_OFF / JIT_ON / JIT_AUTO (None = library default, AUTO)."""
+    def __init__(self, config: RaytracerConfig | None = None, device: int | None = None, jit: int | None = None,
+                 mesh_build: int | None = None):
+        """jit: abi.JIT_OFF / JIT_ON / JIT_AUTO (None = library default, AUTO).
+        mesh_build: abi.MESH_BUILD_HOST / MESH_BUILD_DEVICE (None = the context's initial policy)."""
         self.config = config or RaytracerConfig()
         self._device = device
         self._jit = jit
+        self._mesh_build = mesh_build
         self._ctx: Context | None = None
 
     @staticmethod
@@ -936,6 +952,8 @@ class Raytracer:
     def ctx(self) -> Context:
         if self._ctx is None:
             self._ctx = Context(self._device, self._jit)
+            if self._mesh_build is not None:
+                self._ctx.set_mesh_build(self._mesh_build)
         return self._ctx
 
     def render(self, objects, lights, materials, camera: Camera) -> np.ndarray:

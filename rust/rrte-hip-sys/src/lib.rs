@@ -168,3 +168,5 @@ pub mod query;
 pub mod mesh;
 // deforming meshes, device-side BVH refit (include/rrte_hip_refit.h): likewise
 pub mod refit;
+// the mesh build policy, device-side BVH build (include/rrte_hip_build.h): likewise
+pub mod build;
