@@ -213,17 +213,25 @@ float4 sphere_bound(const double c_in[3], double r, const float* xf) {
         double w[3];
         for (int k = 0; k < 3; ++k)
             w[k] = (double)xf[0 + k] * c[0] + (double)xf[3 + k] * c[1] + (double)xf[6 + k] * c[2] + xf[9 + k];
-        double sn = 0.0;
+        double sn = 0.0, sm = inf;
         for (int col = 0; col < 3; ++col) {
             double a = xf[col * 3], b = xf[col * 3 + 1], e = xf[col * 3 + 2];
             sn = fmax(sn, sqrt(a * a + b * b + e * e));
+            sm = fmin(sm, sqrt(a * a + b * b + e * e));
         }
+        // the object is tested in its own space: a scale outside [2^-40, 2^40] takes ordinary world
+        // coordinates beyond kCullReachHost there (or back), so it is never culled (NaN fails both)
+        if (!(sm >= 1.0 / kCullReachHost && sn <= kCullReachHost))
+            return make_float4(0.0f, 0.0f, 0.0f, __builtin_huge_valf());
         r *= sn * (1.0 + 1e-5);  // M = R*S (mat4_srt): orthogonal columns, so |M v| <= max column norm * |v|
         c[0] = w[0]; c[1] = w[1]; c[2] = w[2];
     }
     double mag = fmax(fabs(c[0]), fmax(fabs(c[1]), fabs(c[2])));
     r = r * 1.001 + 1e-3 + 1e-5 * mag;
-    if (!(r < 3e38) || !std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]))
+    // never culled: non-finite data, and an object that reaches beyond kCullReach = 2^40 -- the culls
+    // rest on "a hit the reference reports lies inside the bound", which holds while the intersectors'
+    // products of up to three coordinates stay finite in f32 (ray_kernels.hpp, wave_hit_bound)
+    if (!(mag + r < kCullReachHost) || !std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]))
         return make_float4(0.0f, 0.0f, 0.0f, __builtin_huge_valf());
     return make_float4((float)c[0], (float)c[1], (float)c[2], nextafterf((float)r, __builtin_huge_valf()));
 }
@@ -256,8 +264,11 @@ void assign_mesh_prims(const rrte_scene_ir* s, const MeshData& md, DPrim* prims,
                 continue;
             }
             const double r = ntri ? std::sqrt(r2) * 1.001 + 1e-3 : 0.0;
-            bounds[pi] = (ntri && std::isfinite(r)) ? f4((float)c[0], (float)c[1], (float)c[2], std::nextafter((float)r, INFINITY))
-                                                     : f4(0.0f, 0.0f, 0.0f, ntri ? INFINITY : 0.0f);
+            const double mag = std::fmax(std::fabs(c[0]), std::fmax(std::fabs(c[1]), std::fabs(c[2])));
+            // (as sphere_bound: never culled beyond kCullReachHost; the test is false for non-finite data too)
+            bounds[pi] = (ntri && mag + r < kCullReachHost)
+                             ? f4((float)c[0], (float)c[1], (float)c[2], std::nextafter((float)r, INFINITY))
+                             : f4(0.0f, 0.0f, 0.0f, ntri ? INFINITY : 0.0f);
         }
     }
 }

@@ -50,7 +50,8 @@ void build_mesh_bvhs(const rrte_scene_ir* s, DPrim* prims, MeshData& out, float4
 // The conservative culling sphere of an object whose intersector reports only points inside the
 // sphere (c, r): given in object space when `xf` is non-null (centre through xf, radius by the
 // largest column norm), then inflated so f32 rounding in the intersectors stays inside.  Radius
-// +inf = never culled (r = +inf, non-finite data).
+// +inf = never culled (r = +inf, non-finite data, or an object that reaches beyond kCullReachHost).
+constexpr double kCullReachHost = 0x1p40;  // = kCullReach of ray_kernels.hpp
 float4 sphere_bound(const double c[3], double r, const float* xf);
 
 }  // namespace rrte

@@ -677,14 +677,22 @@ struct SdfPartsProgram {
 };
 
 // Exact "ray leaves the sphere" early-out for any-hit (shadow) rays: origin outside the sphere
-// (cc = |oc|^2 - r^2 > 0) moving away from its centre (hb = oc.d > 0), |d|^2 >= 1/4, t_min >= 2^-57.
-// Then the full test finds nothing in [t_min, t_max]: disc = RN(RN(hb^2) - RN(a cc)) <= RN(hb^2), so
-// sq = RN(sqrt(disc)) <= RN(sqrt(RN(hb^2))), which is hb when hb >= 2^-60 (fl(sqrt(fl(x*x))) = |x| in
-// binary f32 with round-to-nearest, no under/overflow) and <= 2^-60 otherwise; hence -hb + sq <= 2^-60,
-// both roots (-hb -/+ sq)/a are <= 2^-58 < t_min, and the sphere / bounding-sphere test rejects.
+// (cc = |oc|^2 - r^2 > 0) not approaching its centre (0 <= hb = oc.d < 2^63), |d|^2 >= 1/4,
+// t_min >= 2^-57.  Then the full test finds nothing in [t_min, t_max].  hb < 2^63 keeps RN(hb^2)
+// finite, and a cc is a product of two positive numbers, so it is positive, +0 or +inf, never NaN:
+// disc = RN(RN(hb^2) - RN(a cc)) is a number, <= RN(hb^2), and -inf (a miss) when a cc overflows.
+// Otherwise sq = RN(sqrt(disc)) <= RN(sqrt(RN(hb^2))), which is hb when hb >= 2^-60
+// (fl(sqrt(fl(x*x))) = |x| in binary f32 with round-to-nearest while x*x neither overflows nor
+// underflows) and <= 2^-60 otherwise (hb = 0 included); hence -hb + sq <= 2^-60, both roots
+// (-hb -/+ sq)/a are <= 2^-58 < t_min (a = +inf gives -0), and the sphere / bounding-sphere test
+// rejects.  From hb = 2^64 on RN(hb^2) = +inf: with a cc = +inf as well disc is NaN, every comparison
+// of the full test fails and the reference reports a hit with t = NaN -- so the early-out stands down
+// there and the full test answers.  The range of hb is ONE unsigned compare on its bit pattern,
+// bits(hb) < bits(2^63) = 0x5F000000: a negative hb, -0 and NaN all have larger patterns (and go to
+// the full test), so the bound costs no instruction over the "hb > 0" it replaces.
 // Skips the sqrt and divides of, e.g., every shadow ray's test against the ground sphere.
 __device__ __forceinline__ bool leaves_sphere(float hb, float cc, float a, float t_min) {
-    return hb > 0.0f && cc > 0.0f && a >= 0.25f && t_min >= 0x1p-57f;
+    return __float_as_uint(hb) < 0x5F000000u && cc > 0.0f && a >= 0.25f && t_min >= 0x1p-57f;
 }
 
 // SDFObject::intersect, search part -- sphere tracing inside the object's
@@ -1128,6 +1136,15 @@ __device__ __forceinline__ bool mesh_tri_hit(const MeshView& mv, uint32_t k, con
 constexpr uint32_t kBlockThreads = 64u;
 
 constexpr int kMeshStack = 32;  // BVH depth is capped below this at build time
+
+// The magnitude up to which the shortcuts that rest on "a hit the reference reports lies inside the
+// object's bound" hold: below it the intersectors' products of up to three coordinates stay finite
+// in f32.  Beyond it the reference reports hits with t = NaN or +inf for rays that pass nowhere near
+// the object (sphere: hb^2 and a cc both +inf, disc = NaN, every comparison fails), and at such
+// distances its rounding alone decides which triangle of a mesh a ray "hits".  There the shadow and
+// tile culls stand down (wave_hit_bound; bvh.hip gives such objects the radius +inf) and a mesh is
+// scanned in its original order instead of through its BVH (isect_mesh).
+constexpr float kCullReach = 0x1p40f;
 __device__ __forceinline__ uint32_t* mesh_stack() {
     __shared__ uint32_t stk[kMeshStack * kBlockThreads];  // [depth][lane of the workgroup]
     return stk + threadIdx.x;
@@ -1148,7 +1165,12 @@ __device__ __forceinline__ float box_entry(float4 lo, float4 hi, f3 o, f3 inv, f
 // child first and prunes boxes entered beyond the current best; boxes are inflated at build time
 // so the pruning never drops a triangle the test would accept (meshes).  Rays with
 // a non-finite component take the original-order scan (every test then "hits" with t = NaN, as
-// in the reference, and the lowest index wins).  Writes t and the triangle slot (out.sub).
+// in the reference, and the lowest index wins), and so do rays that start beyond kCullReach, rays
+// against a mesh whose root boxes reach beyond it, and rays that start 2^24 or more of the mesh's
+// extents away from it (one ulp of such an origin is larger than the mesh): there the triangle
+// test's own rounding or overflow, not the geometry, decides what the reference reports, and no box
+// bounds that.  A mesh of one leaf (at most four triangles) is always scanned.
+// Writes t and the triangle slot (out.sub).
 template <bool ANY>
 __device__ __forceinline__ bool isect_mesh(const DPrim& pr, const MeshView& mv, const Ray& r, float t_min,
                                            float t_max, Hit& out) {
@@ -1156,7 +1178,23 @@ __device__ __forceinline__ bool isect_mesh(const DPrim& pr, const MeshView& mv, 
     bool found = false;
     float best = kInf;
     uint32_t best_k = 0u, best_orig = 0u;
-    if (!(finite3(r.o) && finite3(r.d))) {
+    bool scan = !(finite3(r.o) && finite3(r.d)) || !(fmaxf(fmaxf(fabsf(r.o.x), fabsf(r.o.y)), fabsf(r.o.z)) < kCullReach);
+    if (count && !(pr.sdf_first & 0x80000000u)) {  // (wave-uniform: the root's two child boxes)
+        const float4* rec = mv.nodes + 4u * pr.sdf_first;
+        const float4 l0 = rec[0], h0 = rec[1], l1 = rec[2], h1 = rec[3];
+        const f3 lo = V(fminf(l0.x, l1.x), fminf(l0.y, l1.y), fminf(l0.z, l1.z));
+        const f3 hi = V(fmaxf(h0.x, h1.x), fmaxf(h0.y, h1.y), fmaxf(h0.z, h1.z));
+        const float m = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fabsf(lo.z)), fmaxf(fmaxf(fabsf(hi.x), fabsf(hi.y)), fabsf(hi.z)));
+        // the ray's start is `dist` (largest-coordinate norm) from the root box of extent `ext`: from
+        // 2^24 extents on, one ulp of the origin is larger than the whole mesh
+        const float ext = fmaxf(fmaxf(hi.x - lo.x, hi.y - lo.y), hi.z - lo.z);
+        const float dist = fmaxf(fmaxf(fmaxf(lo.x - r.o.x, r.o.x - hi.x), fmaxf(lo.y - r.o.y, r.o.y - hi.y)),
+                                 fmaxf(fmaxf(lo.z - r.o.z, r.o.z - hi.z), 0.0f));
+        scan = scan || !(m < kCullReach) || !(dist < 0x1p24f * ext);
+    } else {
+        scan = true;  // the whole mesh is one leaf: the scan is the same few tests, in the original order
+    }
+    if (scan) {
         for (uint32_t i = 0; i < count; ++i) {
             const uint32_t k = mv.perm[base + i];
             float t, u, v;
@@ -1561,7 +1599,12 @@ __device__ __forceinline__ HitBound wave_hit_bound(bool hit, f3 p, f3 n, float b
     // (a NaN or infinite term, or an overflowing sum, marks the lane unusable -- the wave is then
     // not culled), the 1-ulp hardware square root scaled up by 2^-20, and the offset bound
     // bias * |n|_1 >= bias * |n|_2; the cull margin (1e-3 + 1e-4 * scale) dwarfs their rounding
-    const bool use = hit && __builtin_isfinite(((p.x + p.y) + (p.z + n.x)) + (n.y + n.z));
+    // A point beyond kCullReach also marks its lane unusable: the culls rest on "a hit the reference
+    // reports lies inside the object's bound", which holds only while the intersectors' products of up
+    // to three coordinates stay finite -- past that the reference reports hits with t = NaN or inf
+    // for rays that pass nowhere near the object (sphere: hb^2 and a cc both +inf, disc = NaN).
+    const bool use = hit && __builtin_isfinite(((p.x + p.y) + (p.z + n.x)) + (n.y + n.z)) &&
+                     fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fabsf(p.z)) < kCullReach;
     HitBound b;
     b.ext = 0.0f;
     b.unsafe = __any(hit && !use);

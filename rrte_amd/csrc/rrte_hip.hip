@@ -1240,6 +1240,10 @@ void tile_rects(bool enabled, const std::vector<float4>& bounds, const rrte_scen
         return;
     const uint32_t nbx = (p->width + (1u << sh) - 1) >> sh, nby = (p->height + (1u << sh) - 1) >> sh;
     const rrte_camera& cam = s->camera;
+    // an eye beyond kCullReachHost: the reference's own arithmetic overflows there (hits with t = NaN
+    // for rays that pass nowhere near an object), so no tile is culled
+    for (int k = 0; k < 3; ++k)
+        if (!(std::fabs((double)cam.position[k]) < kCullReachHost)) return;
     double q[4] = {cam.rotation[0], cam.rotation[1], cam.rotation[2], cam.rotation[3]};
     const double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     if (!(qn > 0.0) || !std::isfinite(qn)) return;

@@ -109,18 +109,20 @@ def m_vector(m, p):
 
 
 class Hits:
-    """Per-ray hit record arrays (t, p, n, valid)."""
+    """Per-ray hit record arrays (t, p, n, front face, valid)."""
 
     def __init__(self, n):
         self.t = np.full(n, np.inf, np.float32)
         self.p = [np.zeros(n, np.float32) for _ in range(3)]
         self.n = [np.zeros(n, np.float32) for _ in range(3)]
+        self.front = np.zeros(n, bool)
         self.ok = np.zeros(n, bool)
 
     def set(self, mask, t, p, outward, d):
         front = dot(d, outward) < F(0)
         nn = [np.where(front, outward[k], -outward[k]) for k in range(3)]
         self.t = np.where(mask, t, self.t)
+        self.front = np.where(mask, front, self.front)
         for k in range(3):
             self.p[k] = np.where(mask, p[k], self.p[k])
             self.n[k] = np.where(mask, nn[k], self.n[k])
@@ -155,7 +157,7 @@ def intersect(pr, o, d, tmin, tmax, nodes=None):
             hb = dot(oc, d)
             cc = dot(oc, oc) - p[3] * p[3]
             disc = hb * hb - a * cc
-            ok = disc >= F(0)
+            ok = ~(disc < F(0))  # `if discriminant < 0.0 { return None }`: a NaN discriminant goes on
             sq = np.sqrt(np.where(ok, disc, F(0)))
             r1 = (-hb - sq) / a
             r2 = (-hb + sq) / a
@@ -216,7 +218,7 @@ def intersect(pr, o, d, tmin, tmax, nodes=None):
                 b = F(2) * (oc[0] * ld[0] + oc[2] * ld[2] - k2 * (oc[1] - hh) * ld[1])
                 cc = oc[0] * oc[0] + oc[2] * oc[2] - k2 * (oc[1] - hh) * (oc[1] - hh)
             disc = b * b - F(4) * a * cc
-            ok0 = disc >= F(0)
+            ok0 = ~(disc < F(0))  # as the sphere's (primitives.rs:436,539); the capsule's tests are `>= 0.0`
             sq = np.sqrt(np.where(ok0, disc, F(0)))
             done = ~ok0
             for t in ((-b - sq) / (F(2) * a), (-b + sq) / (F(2) * a)):

@@ -19,9 +19,11 @@ BUILD_RS = ROOT / "rust" / "rrte-hip-sys" / "src" / "build.rs"
 FIELDS = ["device_builds", "host_fallbacks", "policy", "depth"]
 OFFSETS = {"device_builds": 0, "host_fallbacks": 8, "policy": 16, "depth": 20}
 FUNCTIONS = {"rrte_hip_set_mesh_build", "rrte_hip_build_info"}
-# rrte_hip_build_id of the commit before this header: ray_kernels.hpp, device_scene.hpp and rrte_hip.h
-# are untouched, so the JIT caches and the committed counter profiles stay valid
-PARENT_BUILD_ID = "027c2cd794e4ea10a4daf2982fd7a101"
+# rrte_hip_build_id of the device code as committed: whoever edits ray_kernels.hpp, device_scene.hpp or
+# rrte_hip.h moves it knowingly (the JIT caches and the committed counter profiles go stale with it).
+# The header of this file left it at 027c2cd794e4ea10a4daf2982fd7a101; the edge-case ray bank moved it:
+# leaves_sphere bounded by hb < 2^63, the culls and the mesh walk standing down (ray_kernels.hpp).
+PINNED_BUILD_ID = "a37e396d93f8eadcea26e8ff40191b25"
 
 
 def _header_text():
@@ -110,5 +112,5 @@ def test_no_name_is_shared_and_the_other_headers_are_unchanged():
     assert '#include "rrte_hip.h"' in HEADER.read_text()
 
 
-def test_the_device_code_identity_is_the_parents():
-    assert abi.build_id() == PARENT_BUILD_ID
+def test_the_device_code_identity_is_the_pinned_one():
+    assert abi.build_id() == PINNED_BUILD_ID
