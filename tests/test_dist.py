@@ -1,5 +1,5 @@
 """Multi-rank row-band composition on CPU (gloo, world_size 2, 3 and 4), in the layout of the batched GPU
-path (rrte_hip.hip render_batch / flush_batch): each rank renders the bands the frame's band partition
+path (gather.hip render_batch / flush_batch): each rank renders the bands the frame's band partition
 gives it (rrte_hip_band_layout: sky bands on the root, the rest round robin at the root:peer ratio;
 the oracle stands in for the per-rank kernel); the ROOT writes its own bands straight into the frame at their
 image rows (KParams::out_image_rows), every PEER packs its rows as ray_kernel does for a rank -- RGB24,

@@ -2,7 +2,7 @@
 (scene: examples/sdf-showcase/src/main.rs:168-381 layout with real SDFs).
 
 At 4K the frame is wider than 2048 pixels, so camera-ray tile culling switches from 8x8 tiles to
-16x16 blocks (rrte_hip.hip fill_tile_rects); every rank's share of a multi-GPU frame maps its packed
+16x16 blocks (launch_plan.hip fill_tile_rects); every rank's share of a multi-GPU frame maps its packed
 16-row bands to interleaved image rows (ray_kernels.hpp image_row).  Each rank of N = 2, 4, 8 is
 rendered on this GPU exactly as it would be on its own (RRTE_EMULATE_RANK=N:R: that rank's bands,
 packed) and its linear image rows must equal the ORACLE's rows bit for bit, with the oracle's

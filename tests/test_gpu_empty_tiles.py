@@ -1,4 +1,4 @@
-"""All-miss tiles (ray_kernels.hpp ray_kernel_body, rrte_hip.hip tile_rects): a ground sphere that
+"""All-miss tiles (ray_kernels.hpp ray_kernel_body, launch_plan.hip tile_rects): a ground sphere that
 reaches the eye plane gets a rectangle bounded above by its horizon, and a tile outside every object's
 rectangle writes the background without casting a ray.  Neither may change a bit: frames with the
 rectangles on equal frames with RRTE_TILE_CULL=0 -- linear f32 images, RGBA8 frames and shadow-ray

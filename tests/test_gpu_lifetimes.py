@@ -111,7 +111,7 @@ def test_check_word_reports_a_bad_slot(monkeypatch):
 
 
 def test_check_word_reports_a_bad_scene_record(monkeypatch):
-    """The device check of the uploaded scene (rrte_hip.hip scene_records_check, RRTE_DEBUG bit 2):
+    """The device check of the uploaded scene (scene_upload.hip scene_records_check, RRTE_DEBUG bit 2):
     the uploaded objects' kinds, SDF node ranges and CSG-guard links are checked on the device copy the
     kernels read.  Clean uploads of SDF scenes with guards read 0; RRTE_FAULT_BAD_SLOT=2 puts an
     out-of-range kind into object 0 of the device copy only, which must report code 16 (the kernels skip

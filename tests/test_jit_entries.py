@@ -4,7 +4,7 @@ ground sphere's tile rectangle, checked without a GPU.
 test_jit_resources.py reads the first kernel of the resource remarks; a module now has two (the
 general entry and the plain one, rrte_amd/csrc/jit.hip), and a spilled kernel-argument block in
 either is the ~10x regression that test exists for.  The rectangle of a sphere that reaches the eye
-plane (rrte_hip.hip tile_rects) is compared with a brute-force scan of the pixel-centre rays in
+plane (launch_plan.hip tile_rects) is compared with a brute-force scan of the pixel-centre rays in
 double precision: no tile that holds a hit may lie outside it."""
 import ctypes as C
 import re

@@ -16,7 +16,9 @@ mkdir -p "$OUT/this" "$OUT/other"
 emit() {  # <tree> <dir>: the library's assembly, then every specialised kernel with its resource line
     local tree=$1 dir=$2 s
     make -C "$tree/rrte_amd/csrc" all isa > "$dir/make.log" 2>&1 || return 1
-    cp "$tree/build/isa/rrte_hip.s" "$tree/build/isa/mesh_refit.s" "$dir/" || return 1
+    for s in $(make -s -C "$tree/rrte_amd/csrc" print-src 2>/dev/null || echo rrte_hip.hip mesh_refit.hip mesh_build.hip); do  # one per unit (a tree from before print-src: its three)
+        cp "$tree/build/isa/${s%.hip}.s" "$dir/" || return 1
+    done
     : > "$dir/resources.txt"
     for s in $SCENES; do
         echo "$s full: $(cd "$tree" && bash tools/jit_isa.sh $s "$dir/jit_$s.s" | sed -n '1s/ \[-Rpass[^]]*\]//gp')" >> "$dir/resources.txt" || return 1

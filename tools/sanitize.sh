@@ -12,8 +12,11 @@ SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-fram
 HSAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer"
 cd $R/rrte_amd/csrc
 make -s jit_headers.inc
-for f in rrte_hip scene_accel jit bvh mesh_refit mesh_build sdf_guard scene_io; do
-  [ $B/$f.o -nt $f.hip ] && [ $B/$f.o -nt ray_kernels.hpp ] && [ $B/$f.o -nt device_scene.hpp ] && continue
+UNITS=$(make -s print-src | sed 's/\.hip//g')  # the Makefile's SRC: the one list of translation units
+OBJS=$(for f in $UNITS; do printf '%s ' $B/$f.o; done)
+HDR_NEWEST=$(ls -t *.hpp *.inc $R/include/*.h | head -1)  # (an object older than ANY header is rebuilt: rrte_ctx is shared)
+for f in $UNITS; do
+  [ $B/$f.o -nt $f.hip ] && [ $B/$f.o -nt $HDR_NEWEST ] && continue
   /opt/rocm/bin/hipcc -std=c++17 -O1 -g --offload-arch=gfx950 -ffp-contract=off -fPIC $HSAN -I/opt/rocm/include -c $f.hip -o $B/$f.o &
 done
 $CLANG -std=c11 $SAN -ffp-contract=off -pthread -c $R/oracle/rrte_oracle.c -o $B/rrte_oracle.o &
@@ -23,7 +26,7 @@ done
 $CLANG++ -std=c++17 $SAN -I$R/include -c $R/tests/cpp/sanitize_driver.cpp -o $B/sanitize_driver.o &
 wait
 $CLANG++ $SAN -o $B/sanitize_driver $B/sanitize_driver.o $B/rrte_renderer.o $B/examples.o $B/rrte_oracle.o \
-  $B/rrte_hip.o $B/scene_accel.o $B/jit.o $B/bvh.o $B/mesh_refit.o $B/mesh_build.o $B/sdf_guard.o $B/scene_io.o -L/opt/rocm/lib -lamdhip64 -lrccl -lhiprtc -pthread -lm \
+  $OBJS -L/opt/rocm/lib -lamdhip64 -lrccl -lhiprtc -pthread -lm \
   -Wl,-rpath,/opt/rocm/lib
 # leaks inside the ROCm runtime / comgr (not ours) are suppressed by library; ours are reported
 cat > $B/lsan.supp <<'SUPP'

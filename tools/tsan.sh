@@ -31,8 +31,11 @@ if [ "${1:-}" = gpu-run ]; then
 fi
 cd $R/rrte_amd/csrc
 make -s jit_headers.inc
-for f in rrte_hip scene_accel jit bvh mesh_refit mesh_build sdf_guard scene_io; do
-  [ $B/$f.o -nt $f.hip ] && [ $B/$f.o -nt ray_kernels.hpp ] && [ $B/$f.o -nt device_scene.hpp ] && continue
+UNITS=$(make -s print-src | sed 's/\.hip//g')  # the Makefile's SRC: the one list of translation units
+OBJS=$(for f in $UNITS; do printf '%s ' $B/$f.o; done)
+HDR_NEWEST=$(ls -t *.hpp *.inc $R/include/*.h | head -1)  # (an object older than ANY header is rebuilt: rrte_ctx is shared)
+for f in $UNITS; do
+  [ $B/$f.o -nt $f.hip ] && [ $B/$f.o -nt $HDR_NEWEST ] && continue
   /opt/rocm/bin/hipcc -std=c++17 -O1 -g --offload-arch=gfx950 -ffp-contract=off -fPIC $HSAN -I/opt/rocm/include -c $f.hip -o $B/$f.o &
 done
 $CLANG -std=c11 $SAN -ffp-contract=off -pthread -c $R/oracle/rrte_oracle.c -o $B/rrte_oracle.o &
@@ -44,12 +47,12 @@ $CLANG++ -std=c++17 $SAN -I$R/include -c $R/tests/cpp/tsan_gpu_driver.cpp -o $B/
 wait
 if [ "${1:-}" = gpu-build ]; then
   $CLANG++ $SAN -o $R/rrte_amd/lib/tsan_gpu_driver $B/tsan_gpu_driver.o $B/rrte_renderer.o $B/examples.o \
-    $B/rrte_hip.o $B/scene_accel.o $B/jit.o $B/bvh.o $B/mesh_refit.o $B/mesh_build.o $B/sdf_guard.o $B/scene_io.o -L/opt/rocm/lib -lamdhip64 -lrccl -lhiprtc -pthread -lm \
+    $OBJS -L/opt/rocm/lib -lamdhip64 -lrccl -lhiprtc -pthread -lm \
     -Wl,-rpath,/opt/rocm/lib
   exit 0
 fi
 $CLANG++ $SAN -o $B/tsan_driver $B/tsan_driver.o $B/rrte_renderer.o $B/examples.o $B/rrte_oracle.o \
-  $B/rrte_hip.o $B/scene_accel.o $B/jit.o $B/bvh.o $B/mesh_refit.o $B/mesh_build.o $B/sdf_guard.o $B/scene_io.o -L/opt/rocm/lib -lamdhip64 -lrccl -lhiprtc -pthread -lm \
+  $OBJS -L/opt/rocm/lib -lamdhip64 -lrccl -lhiprtc -pthread -lm \
   -Wl,-rpath,/opt/rocm/lib
 # halt_on_error: the first race ends the run with TSan's report and a non-zero status
 TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1" $B/tsan_driver
