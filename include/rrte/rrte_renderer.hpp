@@ -295,9 +295,12 @@ public:
 };
 
 // ----------------------------------------------------- SDF / CSG / deformers (README.md:458-510)
+// A sphere containing the zero set, and the level gain g >= 1: the sublevel set {f <= L}, L >= 0,
+// lies in the sphere grown by g * L (1 for an exact distance; DESIGN.md §6 'Bounds').
 struct Bound {
     double c[3];
     double r;
+    double g = 1.0;
 };
 class SDF {
 public:

@@ -162,6 +162,41 @@ Scene kitchen_sink(uint32_t w, uint32_t h, Mode mode) {
     return s;
 }
 
+Scene sdf_bounds(uint32_t w, uint32_t h, Mode mode) {
+    // shapes whose bounding sphere is more than the operands' spheres plus k (DESIGN.md §6 'Bounds'):
+    // negative sizes, smooth unions of scaled, of inexact and of nested operands
+    Scene s;
+    auto m = lam(0.7f, 0.5f, 0.3f);
+    using CO = CSGOperation;
+    const Vec3 X(1.0f, 0.0f, 0.0f), Y(0.0f, 1.0f, 0.0f), cc(2.2f, 1.0f, 1.0f), o(0.0f, 0.0f, 0.0f), p(0.3f, 0.5f, -0.2f);
+    auto tapered = [&](float x) { return deformed(sdf_sphere(Vec3(x, 0.0f, 0.0f), 0.5), taper(Y, 6.0f, 6.0f, 1.0f)); };
+    auto thin = [&](float x) { return sdf_ellipsoid(Vec3(x, 0.0f, 0.0f), Vec3(1.5f, 0.1f, 1.5f)); };
+    const SDFRef sdfs[] = {
+        sdf_capsule(cc, 0.45, -0.6),
+        sdf_capsule(cc, 0.3, -0.8),
+        sdf_capsule(cc, -0.3, 0.8),
+        sdf_sphere(cc, -0.4),
+        sdf_torus(cc, -0.7, 0.25),
+        sdf_ring(cc, 0.7, -0.2),
+        sdf_ellipsoid(cc, Vec3(-0.9f, 0.5f, 0.7f)),
+        csg(tapered(0.0f), tapered(0.02f), CO::SmoothUnion, 0.5f),
+        csg(thin(0.0f), thin(0.2f), CO::SmoothUnion, 0.5f),
+        csg(sdf_prism(p, Vec3(1.0f, 1.2f, 0.6f)), sdf_box(o, Vec3(0.5f, 0.5f, 0.5f)), CO::SmoothUnion, 0.4f),
+        csg(csg(thin(0.0f), sdf_sphere(o, 1.0), CO::Intersection), csg(sdf_sphere(p, 0.8), thin(0.1f), CO::Difference),
+            CO::SmoothUnion, 0.3f),
+        csg(csg(thin(0.0f), sdf_sphere(p, 0.4), CO::SmoothUnion, 0.2f), sdf_capsule(p, 0.2, 0.6), CO::SmoothUnion, 0.6f),
+        deformed(csg(thin(0.0f), sdf_sphere(p, 0.4), CO::Union),
+                 chain(taper(X, 1.0f, 2.0f, 1.0f, p), twist(Y, 0.5f, o))),
+        csg(deformed(csg(thin(0.0f), sdf_sphere(p, 0.4), CO::Union), chain(taper(X, 1.0f, 2.0f, 1.0f, p), twist(Y, 0.5f, o))),
+            sdf_sphere(o, 0.3), CO::SmoothUnion, 0.25f),
+    };
+    for (const auto& f : sdfs) s.objects.push_back(std::make_shared<SDFObject>(f, m));
+    s.lights = showcase_lights();
+    s.camera = camera(w, h, Vec3(0.0f, 8.0f, 20.0f), Vec3(0.0f, 2.0f, 0.0f), 45.0f);
+    s.config = config(w, h, Color{0.05f, 0.05f, 0.08f, 1.0f}, mode);
+    return s;
+}
+
 Scene instance_demo(uint32_t w, uint32_t h, Mode mode, std::shared_ptr<Mesh> ball, std::shared_ptr<Mesh> ring) {
     Scene s;
     // rrte_amd/scenes.py Q_Y90, Q_X45, Q_Y45, Q_X45_Y45 and INSTANCE_DEMO_PLACEMENTS
@@ -204,6 +239,7 @@ Scene by_name(const std::string& name, uint32_t w, uint32_t h, Mode mode) {
     if (name == "advanced-demo") return advanced_demo(w, h, mode);
     if (name == "sdf-showcase") return sdf_showcase(w, h, mode);
     if (name == "kitchen-sink") return kitchen_sink(w, h, mode);
+    if (name == "sdf-bounds") return sdf_bounds(w, h, mode);
     throw std::invalid_argument("unknown scene " + name);
 }
 

@@ -19,6 +19,7 @@ Scene basic_demo(uint32_t w, uint32_t h, rrte_renderer::Mode mode);     // examp
 Scene advanced_demo(uint32_t w, uint32_t h, rrte_renderer::Mode mode);  // examples/advanced-demo/src/main.rs:238-322
 Scene sdf_showcase(uint32_t w, uint32_t h, rrte_renderer::Mode mode);   // sdf-showcase layout with real SDFs
 Scene kitchen_sink(uint32_t w, uint32_t h, rrte_renderer::Mode mode);   // every kind (tests/test_cpp_mirror.py twin)
+Scene sdf_bounds(uint32_t w, uint32_t h, rrte_renderer::Mode mode);     // bounding-sphere cases (same twin)
 // rrte_amd/scenes.py instance_demo over the caller's two base meshes (`ball` stands on the ground and is
 // also listed as a plain mesh; `ring` is only instanced): eight instances under rigid, uniformly scaled,
 // non-uniformly scaled and mirrored transforms.  The procedural generators live in rrte_amd/mesh.py.

@@ -67,7 +67,7 @@ uint32_t axis_index(Vec3 a) {
 
 Bound about_pivot(Vec3 pivot, Bound b) {
     const double p[3] = {(double)pivot.x, (double)pivot.y, (double)pivot.z};
-    return Bound{{p[0], p[1], p[2]}, dist3(p, b.c) + b.r};
+    return Bound{{p[0], p[1], p[2]}, dist3(p, b.c) + b.r, b.g};
 }
 
 rrte_light light_struct(uint32_t kind, Color color, float intensity, Vec3 position = rrte_math::ZERO,
@@ -338,7 +338,8 @@ namespace {
 
 class Leaf : public SDF {
 public:
-    Leaf(uint32_t op, Vec3 c, std::vector<float> f, double r) : op_(op), c_(c), f_(std::move(f)), r_(r) {}
+    Leaf(uint32_t op, Vec3 c, std::vector<float> f, double r, double g = 1.0)
+        : op_(op), c_(c), f_(std::move(f)), r_(r), g_(g) {}
     void emit(std::vector<rrte_sdf_node>& out) const override {
         rrte_sdf_node n = node(op_);
         n.f[0] = c_.x;
@@ -347,12 +348,16 @@ public:
         for (size_t k = 0; k < f_.size(); ++k) n.f[3 + k] = f_[k];
         out.push_back(n);
     }
-    Bound bound() const override { return make_bound(c_, r_); }
+    Bound bound() const override {
+        Bound b = make_bound(c_, r_);
+        b.g = g_;
+        return b;
+    }
 private:
     uint32_t op_;
     Vec3 c_;
     std::vector<float> f_;
-    double r_;
+    double r_, g_;
 };
 
 class Composite : public SDF {
@@ -380,12 +385,14 @@ public:
                            ba.c[2] + (bb.c[2] - ba.c[2]) * t},
                           rr};
             }
+            r.g = std::max(ba.g, bb.g);  // either operand's sublevel set
         } else if (op_ == CSGOperation::Difference || op_ == CSGOperation::SmoothDifference) {
             r = ba;
         } else {
             r = ba.r <= bb.r ? ba : bb;
         }
-        r.r = r.r + k;
+        // smin(a, b) <= 0 only where a <= k/4 or b <= k/4: a smooth union bounds those sublevel sets
+        r.r = r.r + (op_ == CSGOperation::SmoothUnion ? std::max(k, r.g * k * 0.25) : k);
         return r;
     }
     bool has_deformer() const override { return a_->has_deformer() || b_->has_deformer(); }
@@ -440,7 +447,7 @@ private:
 
 }  // namespace
 
-SDFRef sdf_sphere(Vec3 c, double r) { return std::make_shared<Leaf>(RRTE_SDF_SPHERE, c, std::vector<float>{(float)r}, r); }
+SDFRef sdf_sphere(Vec3 c, double r) { return std::make_shared<Leaf>(RRTE_SDF_SPHERE, c, std::vector<float>{(float)r}, std::fabs(r)); }
 SDFRef sdf_box(Vec3 c, Vec3 s) {
     const double sx = s.x, sy = s.y, sz = s.z;
     return std::make_shared<Leaf>(RRTE_SDF_BOX, c, std::vector<float>{0.0f, s.x, s.y, s.z},
@@ -452,26 +459,31 @@ SDFRef sdf_cylinder(Vec3 c, double r, double h) {
 SDFRef sdf_prism(Vec3 c, Vec3 s) {
     const double a = (double)s.y * 0.5, b = (double)s.y * 0.433, d = (double)s.z * 0.5;
     return std::make_shared<Leaf>(RRTE_SDF_PRISM, c, std::vector<float>{0.0f, s.x, s.y, s.z},
-                                  std::sqrt(a * a + b * b + d * d));
+                                  std::sqrt(a * a + b * b + d * d), std::sqrt(5.0));  // planes: corners move 2 L in XY, L in Z
 }
 SDFRef sdf_torus(Vec3 c, double R, double r) {
-    return std::make_shared<Leaf>(RRTE_SDF_TORUS, c, std::vector<float>{(float)R, (float)r}, R + r);
+    return std::make_shared<Leaf>(RRTE_SDF_TORUS, c, std::vector<float>{(float)R, (float)r}, std::fabs(R) + std::fabs(r));
 }
 SDFRef sdf_tube(Vec3 c, double ro, double ri, double h) {
     return std::make_shared<Leaf>(RRTE_SDF_TUBE, c, std::vector<float>{(float)ro, (float)ri, (float)h}, std::hypot(ro, h * 0.5));
 }
 SDFRef sdf_ring(Vec3 c, double R, double r) {
-    return std::make_shared<Leaf>(RRTE_SDF_RING, c, std::vector<float>{(float)R, (float)r}, R + r);
+    return std::make_shared<Leaf>(RRTE_SDF_RING, c, std::vector<float>{(float)R, (float)r}, std::fabs(R) + std::fabs(r));
 }
 SDFRef sdf_cone(Vec3 c, double r, double h) {
     return std::make_shared<Leaf>(RRTE_SDF_CONE, c, std::vector<float>{(float)r, (float)h}, std::hypot(r, h * 0.5));
 }
 SDFRef sdf_capsule(Vec3 c, double r, double h) {
-    return std::make_shared<Leaf>(RRTE_SDF_CAPSULE, c, std::vector<float>{(float)r, (float)h}, h * 0.5 + r);
+    return std::make_shared<Leaf>(RRTE_SDF_CAPSULE, c, std::vector<float>{(float)r, (float)h},
+                                  std::fabs(h) * 0.5 + std::fabs(r));
 }
 SDFRef sdf_ellipsoid(Vec3 c, Vec3 radii) {
-    return std::make_shared<Leaf>(RRTE_SDF_ELLIPSOID, c, std::vector<float>{0.0f, radii.x, radii.y, radii.z},
-                                  (double)std::max(radii.x, std::max(radii.y, radii.z)));
+    // k0 (k0 - 1) / k1 is a bound, not a distance: k0 >= |q| / r_max and k1 <= k0 / r_min give
+    // f <= L  =>  |q| <= r_max (1 + L / r_min); a zero radius makes the field NaN (no level sets)
+    const double rx = std::fabs((double)radii.x), ry = std::fabs((double)radii.y), rz = std::fabs((double)radii.z);
+    const double hi = std::max(rx, std::max(ry, rz)), lo = std::min(rx, std::min(ry, rz));
+    return std::make_shared<Leaf>(RRTE_SDF_ELLIPSOID, c, std::vector<float>{0.0f, radii.x, radii.y, radii.z}, hi,
+                                  lo > 0.0 ? hi / lo : 1.0);
 }
 SDFRef csg(SDFRef a, SDFRef b, CSGOperation op, float k) { return std::make_shared<Composite>(a, b, op, k); }
 
@@ -489,7 +501,9 @@ DeformerRef taper(Vec3 axis, float start, float end, float length, Vec3 pivot) {
         node(RRTE_SDF_TAPER, {pivot.x, pivot.y, pivot.z, start, end, length}, {axis_index(axis)}), pivot,
         [](const SimpleDeformer& d, Bound b) {
             Bound p = about_pivot(d.pivot, b);
-            p.r = p.r * std::max(1.0, std::max(std::fabs(d.pa), std::fabs(d.pb)));
+            const double s = std::max(1.0, std::max(std::fabs(d.pa), std::fabs(d.pb)));
+            p.r = p.r * s;
+            p.g = p.g * s;  // the one deformer that scales space scales the level sets with it
             return p;
         },
         (double)start, (double)end);

@@ -393,6 +393,12 @@ class SDF:
         """(center, radius) of a sphere containing the zero set."""
         raise NotImplementedError
 
+    def level_gain(self) -> float:
+        """g >= 1 such that the sublevel set {f <= L}, L >= 0, lies in the bound's sphere grown by
+        g * L (DESIGN.md §6 'Bounds').  1 for an exact distance; a smooth union needs it because
+        smooth_min lowers the field by up to k/4."""
+        return 1.0
+
     def has_deformer(self) -> bool:
         return False
 
@@ -424,7 +430,7 @@ class SDFSphere(_Leaf):
         return [*self.center, self.params[0]]
 
     def bound(self):
-        return (tuple(map(float, self.center)), float(self.params[0]))
+        return (tuple(map(float, self.center)), abs(float(self.params[0])))
 
 
 class SDFBox(_Leaf):  # size = full extents, like Cube
@@ -460,6 +466,10 @@ class SDFPrism(_Leaf):  # size: triangle in XY (size.y = triangle size), depth s
         # |x|*0.866 + y*0.5 <= sy/4 and -y <= sy/4: the triangle spans y in [-sy/4, sy/2], |x| <= sy*0.433
         return (tuple(map(float, self.center)), math.sqrt((s[1] * 0.5) ** 2 + (s[1] * 0.433) ** 2 + (s[2] * 0.5) ** 2))
 
+    def level_gain(self):
+        # planes, not a distance: at level L the 60-degree corners move out by 2 L in XY and L in Z
+        return math.sqrt(5.0)
+
 
 class SDFTorus(_Leaf):  # (major, minor), ring in XZ
     OP = abi.SDF_TORUS
@@ -468,7 +478,7 @@ class SDFTorus(_Leaf):  # (major, minor), ring in XZ
         return [*self.center, self.params[0], self.params[1]]
 
     def bound(self):
-        return (tuple(map(float, self.center)), float(self.params[0]) + float(self.params[1]))
+        return (tuple(map(float, self.center)), abs(float(self.params[0])) + abs(float(self.params[1])))
 
 
 class SDFTube(_Leaf):  # (outer, inner, height)
@@ -489,7 +499,7 @@ class SDFRing(_Leaf):  # (major, minor), standing ring in XY
         return [*self.center, self.params[0], self.params[1]]
 
     def bound(self):
-        return (tuple(map(float, self.center)), float(self.params[0]) + float(self.params[1]))
+        return (tuple(map(float, self.center)), abs(float(self.params[0])) + abs(float(self.params[1])))
 
 
 class SDFCone(_Leaf):  # (radius, height), apex +Y
@@ -511,7 +521,7 @@ class SDFCapsule(_Leaf):  # (radius, height)
 
     def bound(self):
         r, h = map(float, self.params[:2])
-        return (tuple(map(float, self.center)), h * 0.5 + r)
+        return (tuple(map(float, self.center)), abs(h) * 0.5 + abs(r))
 
 
 class SDFEllipsoid(_Leaf):  # radii (x, y, z)
@@ -521,7 +531,13 @@ class SDFEllipsoid(_Leaf):  # radii (x, y, z)
         return [*self.center, 0.0, *vec3(self.params[0])]
 
     def bound(self):
-        return (tuple(map(float, self.center)), max(float(v) for v in vec3(self.params[0])))
+        return (tuple(map(float, self.center)), max(abs(float(v)) for v in vec3(self.params[0])))
+
+    def level_gain(self):
+        # k0 (k0 - 1) / k1 is a bound, not a distance: with k0 >= |q| / r_max and k1 <= k0 / r_min,
+        # f <= L gives |q| <= r_max (1 + L / r_min).  A zero radius makes the field NaN: no level sets.
+        rs = [abs(float(v)) for v in vec3(self.params[0])]
+        return max(rs) / min(rs) if min(rs) > 0.0 else 1.0
 
 
 _CSG_OPS = {
@@ -560,7 +576,20 @@ class CSGComposite(SDF):
             c, r = ba
         else:
             c, r = ba if ba[1] <= bb[1] else bb
+        if self.op == "smooth_union":
+            # smin(a, b) <= 0 only where a <= k/4 or b <= k/4: bound those sublevel sets
+            return (c, r + max(k, self.level_gain() * k * 0.25))
         return (c, r + k)
+
+    def level_gain(self):
+        # union: either operand's sublevel set; smooth union: bound() covers level k/4, and
+        # smin <= L needs a or b <= L + k/4; the other ops only raise the left (or smaller) operand
+        ga, gb = self.a.level_gain(), self.b.level_gain()
+        if self.op in ("union", "smooth_union"):
+            return max(ga, gb)
+        if self.op in ("difference", "smooth_difference"):
+            return ga
+        return ga if self.a.bound()[1] <= self.b.bound()[1] else gb
 
     def has_deformer(self):
         return self.a.has_deformer() or self.b.has_deformer()
@@ -576,6 +605,11 @@ class Deformer:
     def grow(self, c, r):
         """Bound of the deformed shape given the undeformed bound (c, r)."""
         raise NotImplementedError
+
+    def level_gain(self, g: float) -> float:
+        """The deformed shape's level gain given the undeformed one: `grow` maps the sphere of any
+        sublevel set, so only a deformer that scales space (taper) changes it."""
+        return g
 
     def chain(self, other: "Deformer") -> "ChainDeformer":
         return ChainDeformer([self, other])
@@ -598,6 +632,11 @@ class ChainDeformer(Deformer):
         for p in reversed(self.parts):
             c, r = p.grow(c, r)
         return c, r
+
+    def level_gain(self, g):
+        for p in reversed(self.parts):
+            g = p.level_gain(g)
+        return g
 
 
 def _about_pivot(pivot, c, r):
@@ -639,6 +678,9 @@ class TaperDeformer(Deformer):  # scale across `axis` from `start` to `end` over
     def grow(self, c, r):
         pc, pr = _about_pivot(self.pivot, c, r)
         return pc, pr * max(1.0, abs(float(self.start)), abs(float(self.end)))
+
+    def level_gain(self, g):
+        return g * max(1.0, abs(float(self.start)), abs(float(self.end)))
 
 
 class NoiseDeformer(Deformer):  # p + amplitude * fbm3(frequency * (p - pivot))
@@ -691,6 +733,9 @@ class DeformedSDF(SDF):
     def bound(self):
         c, r = self.sdf.bound()
         return self.deformer.grow(c, r)
+
+    def level_gain(self):
+        return self.deformer.level_gain(self.sdf.level_gain())
 
     def has_deformer(self):
         return True

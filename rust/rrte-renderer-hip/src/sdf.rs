@@ -16,15 +16,18 @@ use rrte_renderer::{Material, SceneObject};
 use std::fmt;
 use std::sync::Arc;
 
-/// Conservative bounding sphere (double precision, like the C++ and Python mirrors).
+/// Conservative bounding sphere (double precision, like the C++ and Python mirrors) and the level
+/// gain `g >= 1`: the sublevel set `{f <= L}`, `L >= 0`, lies in the sphere grown by `g * L` (1 for
+/// an exact distance; DESIGN.md §6 'Bounds').
 #[derive(Debug, Clone, Copy)]
 pub struct Bound {
     pub c: [f64; 3],
     pub r: f64,
+    pub g: f64,
 }
 
-fn make_bound(c: Vec3, r: f64) -> Bound {
-    Bound { c: [c.x as f64, c.y as f64, c.z as f64], r }
+fn make_bound(c: Vec3, r: f64, g: f64) -> Bound {
+    Bound { c: [c.x as f64, c.y as f64, c.z as f64], r, g }
 }
 
 fn dist3(a: &[f64; 3], b: &[f64; 3]) -> f64 {
@@ -34,7 +37,7 @@ fn dist3(a: &[f64; 3], b: &[f64; 3]) -> f64 {
 
 fn about_pivot(pivot: Vec3, b: Bound) -> Bound {
     let p = [pivot.x as f64, pivot.y as f64, pivot.z as f64];
-    Bound { c: p, r: dist3(&p, &b.c) + b.r }
+    Bound { c: p, r: dist3(&p, &b.c) + b.r, g: b.g }
 }
 
 /// An invalid SDF description (the C ABI would return RRTE_UNSUPPORTED_PRIM / RRTE_INVALID_ARG).
@@ -107,6 +110,7 @@ struct Leaf {
     c: Vec3,
     f: Vec<f32>,
     r: f64,
+    g: f64,
 }
 
 impl Sdf for Leaf {
@@ -121,7 +125,7 @@ impl Sdf for Leaf {
         out.push(n);
     }
     fn bound(&self) -> Bound {
-        make_bound(self.c, self.r)
+        make_bound(self.c, self.r, self.g)
     }
 }
 
@@ -167,6 +171,7 @@ impl Sdf for Composite {
                         c: [ba.c[0] + (bb.c[0] - ba.c[0]) * t, ba.c[1] + (bb.c[1] - ba.c[1]) * t,
                             ba.c[2] + (bb.c[2] - ba.c[2]) * t],
                         r: rr,
+                        g: ba.g.max(bb.g),
                     }
                 }
             }
@@ -179,7 +184,11 @@ impl Sdf for Composite {
                 }
             }
         };
-        r.r += k;
+        if matches!(self.op, CsgOperation::Union | CsgOperation::SmoothUnion) {
+            r.g = ba.g.max(bb.g); // either operand's sublevel set
+        }
+        // smin(a, b) <= 0 only where a <= k/4 or b <= k/4: a smooth union bounds those sublevel sets
+        r.r += if self.op == CsgOperation::SmoothUnion { k.max(r.g * k * 0.25) } else { k };
         r
     }
     fn has_deformer(&self) -> bool {
@@ -259,37 +268,42 @@ impl Sdf for Deformed {
 
 // ------------------------------------------------------------------ builders (README.md:303-328)
 pub fn sdf_sphere(c: Vec3, r: f64) -> SdfRef {
-    Arc::new(Leaf { op: RRTE_SDF_SPHERE, c, f: vec![r as f32], r })
+    Arc::new(Leaf { op: RRTE_SDF_SPHERE, c, f: vec![r as f32], r: r.abs(), g: 1.0 })
 }
 pub fn sdf_box(c: Vec3, s: Vec3) -> SdfRef {
     let (sx, sy, sz) = (s.x as f64, s.y as f64, s.z as f64);
-    Arc::new(Leaf { op: RRTE_SDF_BOX, c, f: vec![0.0, s.x, s.y, s.z], r: 0.5 * (sx * sx + sy * sy + sz * sz).sqrt() })
+    Arc::new(Leaf { op: RRTE_SDF_BOX, c, f: vec![0.0, s.x, s.y, s.z], r: 0.5 * (sx * sx + sy * sy + sz * sz).sqrt(), g: 1.0 })
 }
 pub fn sdf_cylinder(c: Vec3, r: f64, h: f64) -> SdfRef {
-    Arc::new(Leaf { op: RRTE_SDF_CYLINDER, c, f: vec![r as f32, h as f32], r: r.hypot(h * 0.5) })
+    Arc::new(Leaf { op: RRTE_SDF_CYLINDER, c, f: vec![r as f32, h as f32], r: r.hypot(h * 0.5), g: 1.0 })
 }
 pub fn sdf_prism(c: Vec3, s: Vec3) -> SdfRef {
     let (a, b, d) = (s.y as f64 * 0.5, s.y as f64 * 0.433, s.z as f64 * 0.5);
-    Arc::new(Leaf { op: RRTE_SDF_PRISM, c, f: vec![0.0, s.x, s.y, s.z], r: (a * a + b * b + d * d).sqrt() })
+    Arc::new(Leaf { op: RRTE_SDF_PRISM, c, f: vec![0.0, s.x, s.y, s.z], r: (a * a + b * b + d * d).sqrt(),
+                    g: 5f64.sqrt() }) // planes: corners move 2 L in XY, L in Z
 }
 pub fn sdf_torus(c: Vec3, major: f64, minor: f64) -> SdfRef {
-    Arc::new(Leaf { op: RRTE_SDF_TORUS, c, f: vec![major as f32, minor as f32], r: major + minor })
+    Arc::new(Leaf { op: RRTE_SDF_TORUS, c, f: vec![major as f32, minor as f32], r: major.abs() + minor.abs(), g: 1.0 })
 }
 pub fn sdf_tube(c: Vec3, ro: f64, ri: f64, h: f64) -> SdfRef {
-    Arc::new(Leaf { op: RRTE_SDF_TUBE, c, f: vec![ro as f32, ri as f32, h as f32], r: ro.hypot(h * 0.5) })
+    Arc::new(Leaf { op: RRTE_SDF_TUBE, c, f: vec![ro as f32, ri as f32, h as f32], r: ro.hypot(h * 0.5), g: 1.0 })
 }
 pub fn sdf_ring(c: Vec3, major: f64, minor: f64) -> SdfRef {
-    Arc::new(Leaf { op: RRTE_SDF_RING, c, f: vec![major as f32, minor as f32], r: major + minor })
+    Arc::new(Leaf { op: RRTE_SDF_RING, c, f: vec![major as f32, minor as f32], r: major.abs() + minor.abs(), g: 1.0 })
 }
 pub fn sdf_cone(c: Vec3, r: f64, h: f64) -> SdfRef {
-    Arc::new(Leaf { op: RRTE_SDF_CONE, c, f: vec![r as f32, h as f32], r: r.hypot(h * 0.5) })
+    Arc::new(Leaf { op: RRTE_SDF_CONE, c, f: vec![r as f32, h as f32], r: r.hypot(h * 0.5), g: 1.0 })
 }
 pub fn sdf_capsule(c: Vec3, r: f64, h: f64) -> SdfRef {
-    Arc::new(Leaf { op: RRTE_SDF_CAPSULE, c, f: vec![r as f32, h as f32], r: h * 0.5 + r })
+    Arc::new(Leaf { op: RRTE_SDF_CAPSULE, c, f: vec![r as f32, h as f32], r: h.abs() * 0.5 + r.abs(), g: 1.0 })
 }
 pub fn sdf_ellipsoid(c: Vec3, radii: Vec3) -> SdfRef {
+    // k0 (k0 - 1) / k1 is a bound, not a distance: k0 >= |q| / r_max and k1 <= k0 / r_min give
+    // f <= L  =>  |q| <= r_max (1 + L / r_min); a zero radius makes the field NaN (no level sets)
+    let (rx, ry, rz) = ((radii.x as f64).abs(), (radii.y as f64).abs(), (radii.z as f64).abs());
+    let (hi, lo) = (rx.max(ry.max(rz)), rx.min(ry.min(rz)));
     Arc::new(Leaf { op: RRTE_SDF_ELLIPSOID, c, f: vec![0.0, radii.x, radii.y, radii.z],
-                    r: radii.x.max(radii.y.max(radii.z)) as f64 })
+                    r: hi, g: if lo > 0.0 { hi / lo } else { 1.0 } })
 }
 pub fn csg(a: SdfRef, b: SdfRef, op: CsgOperation, k: f32) -> SdfRef {
     Arc::new(Composite { a, b, op, k })
@@ -313,7 +327,9 @@ pub fn taper(axis: Vec3, start: f32, end: f32, length: f32, pivot: Vec3) -> Resu
         pivot,
         grow: |d, b| {
             let mut p = about_pivot(d.pivot, b);
-            p.r *= 1.0f64.max(d.pa.abs().max(d.pb.abs()));
+            let s = 1.0f64.max(d.pa.abs().max(d.pb.abs()));
+            p.r *= s;
+            p.g *= s; // the one deformer that scales space scales the level sets with it
             p
         },
         pa: start as f64, pb: end as f64, octaves: 0,

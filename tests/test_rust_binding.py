@@ -370,6 +370,28 @@ def test_sdf_object_lowering_matches_the_cpp_mirror():
     assert "sdf->has_deformer() ? 0.6f : 1.0f" in cpp
 
 
+def test_sdf_bound_rules_match_the_cpp_mirror():
+    """The bounding-sphere rules that are more than a sum of sizes (DESIGN.md §6 'Bounds'), term by
+    term in both sources: absolute sizes, the level gains of prism and ellipsoid, the smooth union's
+    k/4 sublevel sets, the taper scaling the gain.  (No Rust toolchain runs here: the comparison is
+    textual, like the rest of this file.)"""
+    cpp = " ".join(_strip_comments(CPP.read_text()).split())
+    sdf = " ".join(_strip_comments(SDF_RS.read_text()).split())
+    pairs = [("std::fabs(h) * 0.5 + std::fabs(r)", "h.abs() * 0.5 + r.abs()"),
+             ("std::fabs(R) + std::fabs(r)", "major.abs() + minor.abs()"),
+             ("std::sqrt(5.0)", "5f64.sqrt()"),
+             ("lo > 0.0 ? hi / lo : 1.0", "if lo > 0.0 { hi / lo } else { 1.0 }"),
+             ("r.g = std::max(ba.g, bb.g);", "r.g = ba.g.max(bb.g);"),
+             ("op_ == CSGOperation::SmoothUnion ? std::max(k, r.g * k * 0.25) : k",
+              "if self.op == CsgOperation::SmoothUnion { k.max(r.g * k * 0.25) } else { k }"),
+             ("p.g = p.g * s;", "p.g *= s;"),
+             ("dist3(p, b.c) + b.r, b.g}", "r: dist3(&p, &b.c) + b.r, g: b.g }")]
+    for c, r in pairs:
+        assert c in cpp, c
+        assert r in sdf, r
+    assert cpp.count("std::fabs(R) + std::fabs(r)") == 2 == sdf.count("major.abs() + minor.abs()")  # torus and ring
+
+
 def _cpp_defaults(cpp, fn):
     """Default arguments of a C++ helper signature: [(name, default or None)]."""
     sig = re.search(fn + r"\((.*?)\)\s*\{", " ".join(cpp.split())).group(1)
