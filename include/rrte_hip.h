@@ -373,7 +373,7 @@ rrte_status rrte_hip_jit_check(const rrte_scene_ir* scene, int mode, char* log, 
 /*   RRTE_FPCHECK_SQRT_HW: control -- the bare v_sqrt_f32 against the correctly rounded sqrt
  *                         (the sweep must find its 1-ulp errors).
  *   RRTE_FPCHECK_GAMMA_U8: every f32 bit pattern in [lo, hi): the kernels' gamma-2.2 byte
- *                          (ray_kernels.hpp gamma22_u8) against to_u8(clamp(powf(c, 1/2.2))).
+ *                          (pixel_encode.hpp gamma22_u8) against to_u8(clamp(powf(c, 1/2.2))).
  *   RRTE_FPCHECK_SQRT_BF: as RRTE_FPCHECK_SQRT for the branch-free form (sqrt_rn_branchfree);
  *                         RRTE_FPCHECK_SQRT sweeps the guarded form (sqrt_rn_guarded). */
 typedef enum rrte_fpcheck {

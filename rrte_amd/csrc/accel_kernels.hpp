@@ -10,12 +10,13 @@
 // that is skipped would have missed on every lane, so best_t, the winner, the SDF t_max narrowing and
 // the tie rule are the linear scan's.
 //
-// The searches are overloads of ray_kernels.hpp's closest_t / occluded on the accelerated scene type:
+// The searches are overloads of search.hpp's closest_t / occluded on the accelerated scene type:
 // ray_kernel_body, shade_lambert, path_step and closest_hit reach them through argument-dependent
-// lookup, so ray_kernels.hpp -- the source of every other kernel, embedded for the scene-specialised
-// ones and hashed into rrte_hip_build_id -- is byte for byte what it was.
+// lookup.  They stay here, with the walk they need, and out of the embedded headers.
 //
-// Included by the host translation unit only (scene-specialised kernels have no accelerated form).
+// Includes ray_kernels.hpp (ray_kernel_body, which the accelerated frame kernel instantiates),
+// ray_query.hpp (the query kernels' attribute path) and scene_accel.hpp.  Included by context.hpp, so by
+// the host translation units only (scene-specialised kernels have no accelerated form).
 #pragma once
 
 #include "ray_kernels.hpp"
@@ -181,7 +182,7 @@ __device__ __forceinline__ void accel_for_each(const AccelView& av, uint64_t gro
     }
 }
 
-// closest_t of ray_kernels.hpp over the candidates: the same body, the same arguments.
+// closest_t of search.hpp over the candidates: the same body, the same arguments.
 __device__ __forceinline__ int closest_t(const SceneViewAccel& sc, const Ray& r, float t_min, float& best_t,
                                          uint32_t& best_sub, uint32_t pmask = ~0u) {
     int idx = -1;
@@ -205,7 +206,7 @@ __device__ __forceinline__ int closest_t(const SceneViewAccel& sc, const Ray& r,
     return idx;
 }
 
-// occluded of ray_kernels.hpp over the candidates (`mask`: the shadow cull's, all ones here -- the
+// occluded of search.hpp over the candidates (`mask`: the shadow cull's, all ones here -- the
 // accelerated kernels are compiled without it -- kept so that the call is the same call).
 __device__ __forceinline__ bool occluded(const SceneViewAccel& sc, const Ray& r, float t_min, float t_max, uint64_t mask,
                                          int self = -1) {

@@ -31,7 +31,7 @@ struct BTri {
 // 24-30 (1..128 triangles), first triangle slot (mesh-local) in bits 0-23.
 constexpr uint32_t kLeafBit = 0x80000000u;
 constexpr uint32_t kSahDepth = 20;     // SAH splits above this depth, index-median splits below
-constexpr uint32_t kMaxDepth = 31;     // < kMeshStack (32) in ray_kernels.hpp
+constexpr uint32_t kMaxDepth = 31;     // < kMeshStack (32) in mesh_walk.hpp
 constexpr uint32_t kBigLeaf = 128;
 
 struct Builder {
@@ -230,7 +230,7 @@ float4 sphere_bound(const double c_in[3], double r, const float* xf) {
     r = r * 1.001 + 1e-3 + 1e-5 * mag;
     // never culled: non-finite data, and an object that reaches beyond kCullReach = 2^40 -- the culls
     // rest on "a hit the reference reports lies inside the bound", which holds while the intersectors'
-    // products of up to three coordinates stay finite in f32 (ray_kernels.hpp, wave_hit_bound)
+    // products of up to three coordinates stay finite in f32 (cull.hpp, wave_hit_bound)
     if (!(mag + r < kCullReachHost) || !std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]))
         return make_float4(0.0f, 0.0f, 0.0f, __builtin_huge_valf());
     return make_float4((float)c[0], (float)c[1], (float)c[2], nextafterf((float)r, __builtin_huge_valf()));

@@ -21,7 +21,7 @@ struct MeshRange {
     double lo[3], hi[3];    // the root's (inflated) box in object space
 };
 
-// Device-ready mesh data for the whole scene (layout: MeshView in ray_kernels.hpp).
+// Device-ready mesh data for the whole scene (layout: MeshView in scene_view.hpp).
 struct MeshData {
     std::vector<float4> nodes;   // 4 per interior record: child 0 box (w link), child 1 box (w link)
     std::vector<float4> tris;    // 3 per triangle slot: v0 (w = index within the mesh), e1, e2
@@ -51,7 +51,7 @@ void build_mesh_bvhs(const rrte_scene_ir* s, DPrim* prims, MeshData& out, float4
 // sphere (c, r): given in object space when `xf` is non-null (centre through xf, radius by the
 // largest column norm), then inflated so f32 rounding in the intersectors stays inside.  Radius
 // +inf = never culled (r = +inf, non-finite data, or an object that reaches beyond kCullReachHost).
-constexpr double kCullReachHost = 0x1p40;  // = kCullReach of ray_kernels.hpp
+constexpr double kCullReachHost = 0x1p40;  // = kCullReach of mesh_walk.hpp
 float4 sphere_bound(const double c[3], double r, const float* xf);
 
 }  // namespace rrte

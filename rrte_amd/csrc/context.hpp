@@ -148,7 +148,6 @@ struct rrte_ctx {
     // frames to the root in ONE ncclGather and de-interleaves them.  Every collective is issued on
     // the one comm stream, in program order; slab k's render stream overlaps slab k-1's gather.
     static constexpr int kMaxBatch = 16, kBatchSlabs = 6;
-    static_assert(kMaxBatch == sizeof(rrte::DeinterleaveTargets::full) / sizeof(uint32_t*), "batch targets");
     uint32_t gather_batch = 1;
     hipStream_t comm_stream = nullptr;
     hipStream_t render_stream[kBatchSlabs] = {};

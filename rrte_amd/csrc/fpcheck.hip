@@ -3,7 +3,7 @@
 
 #include <algorithm>
 
-#include "ray_kernels.hpp"
+#include "pixel_encode.hpp"
 
 using namespace rrte;
 

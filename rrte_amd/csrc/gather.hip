@@ -30,8 +30,70 @@ __global__ void stall_kernel(const uint32_t* flag) {
 
 namespace rrte {
 
+// Root-side de-interleave after the RCCL gather: the gathered buffer holds, per rank (rank_stride
+// bytes each; rank `skip_rank`'s rows -- the root's, rendered in place -- are skipped, ~0u for none),
+// that rank's packed rows of `gridDim.z` frames back to back (frame_stride bytes each,
+// `rows_cap` rows of RGBA8 or RGB24 per frame); frame z goes to full[z] (one frame per launch for
+// per-frame gathers, a batch's frames for rrte_hip_set_gather_batch).  RGB24 slabs are expanded
+// with alpha 255 (the host proved every alpha byte is 255).  VEC4: each lane moves 4 pixels (three
+// dword loads for RGB24 or one dwordx4, one dwordx4 store) instead of 4 byte-wise pixels -- the
+// host picks it when the width is a multiple of 4 and every target is 16-byte aligned (the slab
+// strides are 256-byte aligned).  One workgroup row per image row, blockIdx.x strides the row.
+struct DeinterleaveTargets {
+    uint32_t* full[16];
+};
+template <bool RGB24, bool VEC4>
+__global__ __launch_bounds__(256) void deinterleave_batch_kernel(const uint8_t* __restrict__ gathered,
+                                                                 DeinterleaveTargets t, uint32_t width,
+                                                                 BandMap bm, size_t rank_stride, size_t frame_stride,
+                                                                 uint32_t skip_rank) {
+    const uint32_t y = blockIdx.y;
+    const uint32_t band_rows = bm.band_rows;
+    const uint32_t band = y / band_rows, w = y - band * band_rows;
+    uint32_t local_band = 0;
+    const uint32_t rank = band_owner(bm, band, local_band);
+    if (rank == skip_rank) return;  // the root's own bands: rendered into the frame in place
+    const uint32_t lr = local_band * band_rows + w;
+    constexpr uint32_t bpp = RGB24 ? 3u : 4u;
+    const uint8_t* src = gathered + (size_t)rank * rank_stride + (size_t)blockIdx.z * frame_stride +
+                         (size_t)lr * width * bpp;
+    uint32_t* dst = t.full[blockIdx.z] + (size_t)y * width;
+    const uint32_t step = gridDim.x * blockDim.x;
+    if constexpr (VEC4) {
+        const uint32_t n4 = width >> 2;
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += step) {
+            uint4 o;
+            if constexpr (RGB24) {
+                // pixels 4i..4i+3 = bytes 12i..12i+11 = dwords 3i..3i+2 (little endian)
+                const uint32_t* q = reinterpret_cast<const uint32_t*>(src) + 3u * i;
+                const uint32_t d0 = __builtin_nontemporal_load(q), d1 = __builtin_nontemporal_load(q + 1),
+                               d2 = __builtin_nontemporal_load(q + 2);
+                o.x = d0 | 0xFF000000u;
+                o.y = (d0 >> 24) | (d1 << 8) | 0xFF000000u;
+                o.z = (d1 >> 16) | (d2 << 16) | 0xFF000000u;
+                o.w = (d2 >> 8) | 0xFF000000u;
+            } else {
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src) + i);
+                o = make_uint4(v.x, v.y, v.z, v.w);
+            }
+            reinterpret_cast<uint4*>(dst)[i] = o;
+        }
+    } else {
+        for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < width; x += step) {
+            if constexpr (RGB24) {
+                const uint8_t* q = src + 3u * x;
+                dst[x] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | 0xFF000000u;
+            } else {
+                dst[x] = reinterpret_cast<const uint32_t*>(src)[x];
+            }
+        }
+    }
+}
+static_assert(rrte_ctx::kMaxBatch == sizeof(DeinterleaveTargets::full) / sizeof(uint32_t*), "batch targets");
+
 // Gather slabs carry RGB24 (3 B/pixel, 25 % fewer bytes over xGMI) when every pixel's alpha byte
-// is provably 255.  LAMBERT_SHADOW never lets a light touch alpha (ray_kernels.hpp, shade_lambert):
+// is provably 255.  LAMBERT_SHADOW never lets a light touch alpha (shade.hpp, shade_lambert):
 // a sample's alpha is the background's (miss), 1 (no material, max_depth 0) or 1 + (a*0.1)*0.1 for
 // the material's albedo alpha a, and the pixel's is rclamp((1 + sum of sample alphas) * inv_spp)
 // (the sum starts from BLACK, alpha 1).  With every sample alpha >= 0 (spp 1) or >= 1 (spp n > 1:
@@ -51,7 +113,7 @@ static bool slab_rgb24(const rrte_ctx* c, const rrte_scene_ir* s, const rrte_ren
 // of them to the root in one ncclGather (each rank sends its frames' slices back to back) and
 // de-interleaves every frame into its caller buffer.  Every rank holds the same open batch (same
 // frames in the same order), so the collective matches.
-// De-interleave `n` gathered frames (ray_kernels.hpp deinterleave_batch_kernel) on `st`.
+// De-interleave `n` gathered frames (deinterleave_batch_kernel, above) on `st`.
 static rrte_status deinterleave(rrte_ctx* c, hipStream_t st, const uint8_t* gathered, const DeinterleaveTargets& t,
                                 uint32_t n, uint32_t width, uint32_t height, const BandMap& bm, bool rgb24,
                                 size_t rank_stride, size_t frame_stride, uint32_t skip_rank = ~0u) {

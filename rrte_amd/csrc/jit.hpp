@@ -20,7 +20,7 @@ struct JitKernel {
     bool topology = false;  // a topology kernel (jit_source with JitTopo)
 };
 
-// The host's structural decisions for a TOPOLOGY kernel (ray_kernels.hpp TopoPrim / TopoLight):
+// The host's structural decisions for a TOPOLOGY kernel (scene_view.hpp TopoPrim / TopoLight):
 // per object, whether its SDF program is convex (sdf_convex); per light, whether shadow culling may
 // cull for it (light_record_cullable).
 struct JitTopo {

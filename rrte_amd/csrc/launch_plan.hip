@@ -352,7 +352,7 @@ static BandMap band_layout(const rrte_camera& cam, const std::vector<float4>& bo
     return m;
 }
 
-// Shadow-ray culling (ray_kernels.hpp, shadow_cull) for LAMBERT_SHADOW frames: one lane per object,
+// Shadow-ray culling (cull.hpp, shadow_cull) for LAMBERT_SHADOW frames: one lane per object,
 // so scenes of <= 64 objects; it pays where an occlusion test is expensive (sphere-traced SDF
 // objects) and costs a few percent on all-analytic scenes (measured).  RRTE_CULL=0/1
 // forces it off/on (A/B runs, tests).

@@ -5,9 +5,9 @@
 // kBlockThreads).  The object loop is wave-uniform exactly as in the frame kernel: every lane tests
 // object k at the same time, its record read with scalar loads (load_uniform), however incoherent
 // the rays are.  The search and the attribute path are the frame kernel's own functions
-// (ray_kernels.hpp intersect_at / any_hit_at / mesh_tri_hit / sdf_hit_attributes) with the caller's
-// interval in place of [kp.t_min, +inf), so a query is bit-identical to a loop over
-// SceneObject::intersect (raytracer.rs:103-113).
+// (search.hpp intersect_at / any_hit_at, mesh_walk.hpp mesh_tri_hit, intersect.hpp
+// sdf_hit_attributes) with the caller's interval in place of [kp.t_min, +inf), so a query is
+// bit-identical to a loop over SceneObject::intersect (raytracer.rs:103-113).
 //
 // Tail and finished lanes: the search contains wave-wide operations (the __all of the CSG guards in
 // sdf_guard, readfirstlane in the attribute walk, __all in the any-hit loop), so a lane past
@@ -20,7 +20,7 @@
 #pragma once
 
 #include "../../include/rrte_hip_query.h"
-#include "ray_kernels.hpp"
+#include "shade.hpp"
 
 namespace rrte {
 
@@ -52,14 +52,7 @@ __device__ __forceinline__ void query_attributes(const S& sc, uint32_t i, const 
         if (pr.kind == RRTE_PRIM_SDF) {
             const rrte_sdf_node* nd = sc.nodes + pr.sdf_first;
             if (RRTE_SDF_LEAF_DISPATCH && pr.sdf_count == 1u) {
-                const rrte_sdf_node n = load_uniform(nd);
-                auto leaf = [&](auto opc) {
-                    constexpr uint32_t OP = decltype(opc)::value;
-                    if (n.op == OP)
-                        sdf_hit_attributes(SdfLeafProgram<OP>{load_uniform(reinterpret_cast<const NodeArgs*>(nd->f))}, r,
-                                           t, out);
-                };
-                static_for_leaves(leaf);
+                with_leaf_program(nd, [&](auto, const auto& prog) { sdf_hit_attributes(prog, r, t, out); });
                 return;
             }
             sdf_hit_attributes(SdfProgramT<F>{nd, pr.sdf_count}, r, t, out);

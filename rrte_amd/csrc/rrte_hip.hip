@@ -391,7 +391,7 @@ static rrte_status finish_tile_order(rrte_ctx* c, const LaunchPlan& L, bool prof
 }
 
 // The generic kernel variant for a scene with features `need` (kFeat*): the first of the
-// precompiled feature sets F0, F1, F2 that covers it, else every feature (ray_kernels.hpp SceneView).
+// precompiled feature sets F0, F1, F2 that covers it, else every feature (scene_view.hpp SceneView).
 template <int MODE, bool CULL, uint32_t F0, uint32_t F1, uint32_t F2>
 static void launch_generic(uint32_t need, dim3 grid, dim3 block, hipStream_t st, const KParams& k, const SceneView& sv,
                            const Cull& cl, uint32_t* d_rgba, float4* d_f32, unsigned long long* ctr) {
@@ -409,7 +409,7 @@ static void launch_generic(uint32_t need, dim3 grid, dim3 block, hipStream_t st,
 }
 
 // Whether a launch of the specialised kernel `jk` meets every assumption of its plain entry
-// (ray_kernels.hpp LaunchPlain): one frame into the RGBA8 device buffer `d_rgba` alone, rows packed from
+// (shade.hpp LaunchPlain): one frame into the RGBA8 device buffer `d_rgba` alone, rows packed from
 // image row 0 with no band map, no debug bit, gamma 2.2 and one sample per pixel (SINGLE kernels only
 // have the entry).  Gather slabs, rank shares, multi-frame batches, f32
 // frames, zero-copy frames (rrte_ctx::host_out), RRTE_DEBUG and other gammas

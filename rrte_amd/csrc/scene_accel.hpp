@@ -14,7 +14,7 @@ constexpr uint32_t kAccelLeaf = 4u;          // most objects of one leaf
 constexpr uint32_t kAccelLeafBit = 0x80000000u;
 
 // A link is an interior record index (bit 31 clear) or a leaf (bit 31 set, object count - 1 in bits
-// 24-30, first entry of `leaf_prims` in bits 0-23): the mesh BVH's link (ray_kernels.hpp MeshView).
+// 24-30, first entry of `leaf_prims` in bits 0-23): the mesh BVH's link (scene_view.hpp MeshView).
 // Record k = nodes[16k .. 16k+15], four float4 as the mesh record's: child 0 box min (w = child 0
 // link), child 0 box max (w = split axis), child 1 box min (w = child 1 link), child 1 box max.
 struct AccelTree {

@@ -185,7 +185,7 @@ rrte_status validate(rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_para
 }
 
 // Conservative world-space bounding sphere of one object for wave culling
-// (ray_kernels.hpp, primary_cull/shadow_cull): every point the object's
+// (cull.hpp, shadow_cull): every point the object's
 // intersector can report lies inside it.  Radius +inf = never culled (planes,
 // non-finite data).  Computed in double and inflated, so f32 rounding in the
 // intersectors stays inside.
@@ -320,7 +320,7 @@ static bool scene_same(const rrte_ctx* c, const rrte_scene_ir* s) {
     return true;
 }
 
-// The scene's topology -- what a topology kernel compiles in (jit.hip, ray_kernels.hpp TopoPrim /
+// The scene's topology -- what a topology kernel compiles in (jit.hip, scene_view.hpp TopoPrim /
 // TopoNode / TopoLight) -- as a key, with its structural decisions in `topo`: object kinds and SDF
 // node ranges, node ops and integer arguments (CSG-guard links included), light kinds, per-object
 // SDF convexity (value-dependent for cones) and per-light cullability.  Also stores each SDF

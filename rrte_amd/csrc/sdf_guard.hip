@@ -1,6 +1,6 @@
 // sdf_guard.hip — host analysis of SDF node programs: a conservative bound per CSG subtree and
 // the guards that let a wave skip the right operand of a union / difference exactly
-// (sdf_guard.hpp).  The bounds follow the build-defined leaf formulas of ray_kernels.hpp
+// (sdf_guard.hpp).  The bounds follow the build-defined leaf formulas of sdf_eval.hpp
 // sdf_leaf; each case states why value(p) >= lambda * (|q| - R) for |q| >= R,
 // q = p - centre.
 #include "sdf_guard.hpp"

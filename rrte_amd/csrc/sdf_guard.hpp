@@ -18,7 +18,7 @@ namespace rrte {
 // bound alone decides the op (union: bound >= a; smooth union: h(a, bound) == 1; difference:
 // -bound <= a; smooth difference: h(-a, bound) == 1) the op's result is exactly its left
 // operand and B is not evaluated.  The device takes the early-out only when every active lane
-// of the wave may take it (ray_kernels.hpp sdf_guard), so results are bit-identical with guards
+// of the wave may take it (sdf_eval.hpp sdf_guard), so results are bit-identical with guards
 // on or off.
 constexpr uint32_t kGuardSlot = 2;  // rrte_sdf_node::i[kGuardSlot]
 

@@ -1,7 +1,7 @@
 // search_groups.hpp — the object searches of a scene-specialised kernel, with grouped skip tests
 // (DESIGN.md §21).
 //
-// ray_kernels.hpp's occluded() and closest_t() visit every object of a static scene with a compile-time
+// search.hpp's occluded() and closest_t() visit every object of a static scene with a compile-time
 // index and step over the ones the wave's cull removed: one wave-uniform test and branch per object
 // -- on the 64-bit shadow mask four scalar instructions, 51 times per ray of the headline (17 objects,
 // 3 lights), nearly all of them taken.  The searches below are the same searches -- every object whose
@@ -18,11 +18,12 @@
 // Objects without a mask bit (index >= 64 for the shadow mask, >= 32 for the camera mask) are never
 // skipped, as before; a shadow mask of zero skips every object, as before.
 //
-// This text is no header of the hiprtc program: jit.hip pastes it into the generated translation unit
-// after the definition of rrte_jit::Scene (so it is part of the source the code-object cache key
-// hashes, and no part of the headers rrte_hip_build_id hashes).  The searches are non-template
-// overloads on rrte_jit::Scene: closest_hit() and shade_lambert() reach them through argument-dependent
-// lookup and prefer them to the templates, the way accel_kernels.hpp reaches the generic kernel.
+// An embedded header like the others (the Makefile's DEVICE_HDR), but included by the generated source,
+// not by ray_kernels.hpp: jit.hip's jit_source emits its #include right after the definition of
+// rrte_jit::Scene, which the searches below name.  They are non-template overloads on rrte_jit::Scene:
+// closest_hit() and shade_lambert() reach them through argument-dependent lookup and prefer them to
+// search.hpp's templates, the way accel_kernels.hpp reaches the generic kernel.  Includes nothing (the
+// source has included ray_kernels.hpp by then).
 // -DRRTE_SEARCH_GROUPS=0 (RRTE_JIT_EXTRA_OPTS) leaves the templates in charge (A/B).
 #ifndef RRTE_SEARCH_GROUPS
 #define RRTE_SEARCH_GROUPS 6  // objects per group (3, 4, 6, 8 measured on the headline: DESIGN.md §21)
@@ -107,7 +108,7 @@ __device__ __forceinline__ void closest_groups(const S& sc, const Ray& r, float 
 
 }  // namespace search
 
-// closest_t of ray_kernels.hpp for the specialised scene: strict '<', equal t to the lower index.
+// closest_t of search.hpp for the specialised scene: strict '<', equal t to the lower index.
 __device__ __forceinline__ int closest_t(const rrte_jit::Scene& sc, const Ray& r, float t_min, float& best_t,
                                          uint32_t& best_sub, uint32_t pmask = ~0u) {
     search::Best b{-1, kInf, 0u};
@@ -117,7 +118,7 @@ __device__ __forceinline__ int closest_t(const rrte_jit::Scene& sc, const Ray& r
     return b.idx;
 }
 
-// occluded of ray_kernels.hpp for the specialised scene.
+// occluded of search.hpp for the specialised scene.
 __device__ __forceinline__ bool occluded(const rrte_jit::Scene& sc, const Ray& r, float t_min, float t_max, uint64_t mask,
                                          int self = -1) {
     typedef search::MaskOf<(rrte_jit::Scene::num_prims <= 32u)>::type M;

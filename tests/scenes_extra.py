@@ -175,7 +175,7 @@ def convex_sdf_scene(w, h, mode="lambert_shadow"):
     capsule, intersections and smooth intersections; degenerate sizes: a negative box extent, an inverted capsule) packed
     close together with non-convex controls (torus, union, cone with a negative radius), lit by a
     light near the horizon and one overhead: many grazing shadow rays, and shadow rays that start on
-    one convex object and skim its neighbours (ray_kernels.hpp sdf_march CONVEX)."""
+    one convex object and skim its neighbours (intersect.hpp sdf_march CONVEX)."""
     from rrte_amd import renderer as R
 
     ms = [LambertianMaterial(Color.rgb(*c)) for c in [(0.7, 0.5, 0.3), (0.3, 0.6, 0.8), (0.5, 0.8, 0.4)]]
@@ -207,12 +207,12 @@ def convex_sdf_scene(w, h, mode="lambert_shadow"):
 
 
 def csg_parts_scene(w, h, mode="lambert_shadow"):
-    """Two-leaf CSG objects the part-wise secant early miss applies to (ray_kernels.hpp sdf_parts_plan):
-    unions and smooth unions of two convex leaves (both parts proven), differences and smooth
-    differences with a convex left leaf (the left part proven; the right one may be anything, here a
-    torus too), a large smooth k, degenerate sizes, and controls the plan must leave alone (a union with
-    a torus, a smooth union with k = 0), packed together under a near-horizon light and an overhead
-    one: grazing shadow rays leaving one object and skimming the next."""
+    """Two-leaf CSG objects, none convex as a whole, so the convex secant early miss (intersect.hpp
+    sdf_march CONVEX, sdf_eval.hpp sdf_convex) must leave every one alone: unions and smooth unions of
+    two convex leaves, differences and smooth differences with a convex left leaf (the right one a torus
+    too), a large smooth k, degenerate sizes, a union with a torus and a smooth union with k = 0, packed
+    together under a near-horizon light and an overhead one: grazing shadow rays leaving one object and
+    skimming the next.  (Built for round 6's part-wise exit, since removed: DESIGN.md §14.)"""
     from rrte_amd import renderer as R
 
     ms = [LambertianMaterial(Color.rgb(*c)) for c in [(0.8, 0.4, 0.3), (0.3, 0.7, 0.6), (0.6, 0.6, 0.9)]]

@@ -19,11 +19,13 @@ BUILD_RS = ROOT / "rust" / "rrte-hip-sys" / "src" / "build.rs"
 FIELDS = ["device_builds", "host_fallbacks", "policy", "depth"]
 OFFSETS = {"device_builds": 0, "host_fallbacks": 8, "policy": 16, "depth": 20}
 FUNCTIONS = {"rrte_hip_set_mesh_build", "rrte_hip_build_info"}
-# rrte_hip_build_id of the device code as committed: whoever edits ray_kernels.hpp, device_scene.hpp or
-# rrte_hip.h moves it knowingly (the JIT caches and the committed counter profiles go stale with it).
+# rrte_hip_build_id of the device code as committed: whoever edits an embedded device header (the
+# Makefile's DEVICE_HDR: ray_kernels.hpp and the headers under it, device_scene.hpp, search_groups.hpp,
+# rrte_hip.h) moves it knowingly (the JIT caches and the committed counter profiles go stale with it).
 # The header of this file left it at 027c2cd794e4ea10a4daf2982fd7a101; the edge-case ray bank moved it:
-# leaves_sphere bounded by hb < 2^63, the culls and the mesh walk standing down (ray_kernels.hpp).
-PINNED_BUILD_ID = "a37e396d93f8eadcea26e8ff40191b25"
+# leaves_sphere bounded by hb < 2^63, the culls and the mesh walk standing down (a37e396d93f8eadcea26e8ff40191b25).
+# The split of ray_kernels.hpp into layered headers moved it: the same kernels from another hashed text.
+PINNED_BUILD_ID = "827928e4f1af32f488444308c4ead015"
 
 
 def _header_text():

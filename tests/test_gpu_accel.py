@@ -273,7 +273,7 @@ def test_bounce_rays_walk(n):
 
     Depth 2 is compared with the oracle bit for bit.  Depth 3 cannot be: the device evaluates the
     reference's recursion forward, which is exact up to depth 2 and differs at rounding level beyond
-    (ray_kernels.hpp PathState; tests/test_gpu_parity.py test_stochastic_multibounce_materials), with
+    (shade.hpp PathState; tests/test_gpu_parity.py test_stochastic_multibounce_materials), with
     or without the accelerator -- measured on the 33-object scene, 901 of 9216 floats differ from the
     oracle by one ulp under policy OFF and the same 901 under ON.  So at depth 3 the frame must be
     bit for bit the same context's frame under policy OFF, and meet the oracle under the rule the

@@ -136,17 +136,16 @@ def test_shadow_culling_is_exact(case, jit, monkeypatch):
 @pytest.mark.parametrize("size", [(240, 160), (641, 359)])
 def test_convex_secant_early_miss_is_exact(size, scene, monkeypatch):
     """Scene-specialised any-hit marches of convex SDF objects stop once the secant bound proves
-    that no later step can hit (ray_kernels.hpp sdf_march CONVEX), and those of two-leaf CSG objects
-    once every part their value is bounded by is proven (sdf_parts_plan, round 6).  Exact: the image
+    that no later step can hit (intersect.hpp sdf_march CONVEX); two-leaf CSG objects, which are not
+    convex as a whole, march on (csg_parts: the controls the exit must leave alone).  Exact: the image
     and the shadow-ray count match the oracle bit for bit, and match the same kernel compiled without
-    the early misses (RRTE_JIT_EXTRA_OPTS=-DRRTE_SECANT_EXIT=0), with grazing and near-horizon lights,
-    degenerate sizes and controls the exits must leave alone."""
+    the early miss (RRTE_JIT_EXTRA_OPTS=-DRRTE_SECANT_EXIT=0), with grazing and near-horizon lights
+    and degenerate sizes."""
     fn = se.convex_sdf_scene if scene == "convex" else se.csg_parts_scene
     objs, lights, cam, cfg = fn(*size)
     compare(objs, lights, cam, cfg, jit=abi.JIT_ON)
     out = {}
-    # (the part-wise exit is an off-by-default switch: -DRRTE_PARTS_EXIT=1 checks it)
-    opts = ("", "-DRRTE_PARTS_EXIT=1", "-DRRTE_SECANT_EXIT=0")
+    opts = ("", "-DRRTE_SECANT_EXIT=0")
     for opt in opts:
         monkeypatch.setenv("RRTE_JIT_EXTRA_OPTS", opt)
         rt = Raytracer(cfg, device=0, jit=abi.JIT_ON)
@@ -154,7 +153,7 @@ def test_convex_secant_early_miss_is_exact(size, scene, monkeypatch):
         st = rt.stats()
         assert st.jit_active == 1
         out[opt] = (lin.view(np.uint32).copy(), int(st.shadow_rays))
-    for opt in opts[:2]:
+    for opt in opts[:-1]:
         assert np.array_equal(out[opt][0], out["-DRRTE_SECANT_EXIT=0"][0]), opt
         assert out[opt][1] == out["-DRRTE_SECANT_EXIT=0"][1], opt
 

@@ -1,4 +1,4 @@
-"""The two entry points of a scene-specialised kernel (rrte_amd/csrc/jit.hip, ray_kernels.hpp
+"""The two entry points of a scene-specialised kernel (rrte_amd/csrc/jit.hip, shade.hpp
 LaunchPlain): the plain entry, with an engine frame's launch constants compiled in, renders the bytes
 and counts the shadow rays of the general entry (RRTE_JIT_PLAIN=0), within the usual bar of the oracle
 (u8 <= 1, counts exact); and every launch that breaks one of the plain entry's assumptions -- f32

@@ -1,4 +1,4 @@
-"""Topology-specialised kernels (jit.hip JitTopo, ray_kernels.hpp TopoPrim / TopoNode / TopoLight;
+"""Topology-specialised kernels (jit.hip JitTopo, scene_view.hpp TopoPrim / TopoNode / TopoLight;
 VERDICT r02 #8).  A topology kernel compiles in only the scene's structure and reads every value --
 SDF leaf centres and sizes, smooth-op k, CSG-guard spheres, light positions and intensities, material
 colours -- from the uploaded records, so an animated scene compiles ONE kernel instead of one per

@@ -3,21 +3,16 @@ instance mode, the dump/load round trip of an instance scene, and the scene-spec
 instance_demo compiling for gfx950 (full and topology), with their register and scratch figures."""
 import ctypes as C
 import json
-import re
 import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import instance_ref as ir
+import offline_jit
 from rrte_amd import (Camera, Color, LambertianMaterial, LoweredScene, Mesh, MeshInstance, Sphere, Transform, abi,
                       load_scene_asset, scenes, sceneio)
 from rrte_amd.mesh import icosphere
-
-ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "rrte_amd" / "csrc"
 
 
 def _trs(p):
@@ -125,28 +120,6 @@ def test_dump_load_round_trip_of_an_instance_scene(tmp_path, monkeypatch):
     ld.close()
 
 
-def _resources(src: Path, tmp_path: Path):
-    """VGPRs / SGPRs / scratch of a dumped scene-specialised kernel: hipcc with the JIT's own options
-    (jit.hip rtc_options), as tools/jit_isa.sh compiles it."""
-    inc = tmp_path / "inc"
-    inc.mkdir(exist_ok=True)
-    shutil.copy(ROOT / "include" / "rrte_hip.h", inc / "rrte_hip.h")
-    shutil.copy(CSRC / "ray_kernels.hpp", tmp_path / "ray_kernels.hpp")
-    (tmp_path / "device_scene.hpp").write_text(
-        (CSRC / "device_scene.hpp").read_text().replace("../../include/rrte_hip.h", str(inc / "rrte_hip.h")))
-    text = re.sub(r"^typedef __hip_internal.*$", "", src.read_text(), flags=re.M)
-    cu = tmp_path / (src.stem + "_offline.hip")
-    cu.write_text("#include <hip/hip_runtime.h>\n" + text)
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "--offload-arch=gfx950", "-ffp-contract=off",
-                        "-mllvm", "-amdgpu-sched-strategy=max-ilp", "--cuda-device-only", "-S", "-o",
-                        str(tmp_path / (src.stem + ".s")), "-Rpass-analysis=kernel-resource-usage", str(cu)],
-                       capture_output=True, text=True, timeout=900, cwd=tmp_path)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-3000:]
-    return {k: int(re.search(rf"{re.escape(k)}: (\d+)", out).group(1))
-            for k in ("VGPRs", "SGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]")}
-
-
 @pytest.mark.skipif(shutil.which("/opt/rocm/bin/hipcc") is None, reason="needs hipcc")
 @pytest.mark.parametrize("topo", ["0", "1"])
 def test_instance_demo_kernels_compile_for_gfx950(topo, tmp_path, monkeypatch):
@@ -165,7 +138,7 @@ def test_instance_demo_kernels_compile_for_gfx950(topo, tmp_path, monkeypatch):
     assert abi.load().rrte_hip_jit_check(sc.ref(), 1, log, len(log)) == abi.RRTE_OK, log.value.decode()[:4000]
     text = src.read_text()
     assert ("kTopo = true" in text) == (topo == "1")
-    res = _resources(src, tmp_path)
+    res = offline_jit.resources(src, tmp_path)
     print(f"instance_demo {'topology' if topo == '1' else 'full'} kernel: {res}")
     assert res["ScratchSize [bytes/lane]"] == 0
     assert res["VGPRs"] <= 96 and res["Occupancy [waves/SIMD]"] == 5

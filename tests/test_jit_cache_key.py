@@ -26,7 +26,7 @@ def test_key_changes_with_the_source():
 
 
 def test_an_edited_header_misses_the_cache():
-    """headers_override stands in for the embedded kHdrApi/kHdrDeviceScene/kHdrRayKernels of a
+    """headers_override stands in for the embedded device headers (jit.hip kJitHeaders) of a
     rebuilt library: any change of their text changes the key."""
     src = "#include \"ray_kernels.hpp\"\n"
     base = _key(src)

@@ -10,8 +10,10 @@ import sys; sys.path.insert(0, '$R')
 from rrte_amd import abi, scenes, LoweredScene
 lib = abi.load(); o,l,c,cfg = scenes.SCENES['$SCENE'](64,36); sc = LoweredScene(o,l,c)
 lib.rrte_hip_jit_check(sc.ref(), 1, None, 0)" || exit 1
-mkdir -p $T/inc && cp $R/include/rrte_hip.h $T/inc/ && cp $R/rrte_amd/csrc/device_scene.hpp $R/rrte_amd/csrc/ray_kernels.hpp $T/
-sed -i "s#../../include/rrte_hip.h#$T/inc/rrte_hip.h#" $T/device_scene.hpp
+# the embedded device headers (the Makefile's DEVICE_HDR) side by side under their plain names, as hiprtc
+# gets them (jit.hip rtc_compile): an include that reaches one through a directory loses the directory
+for h in $(make -s -C $R/rrte_amd/csrc print-device-hdr); do cp $R/rrte_amd/csrc/$h $T/ || exit 1; done
+for h in $T/*.h*; do sed -i "s#^\(\#include \"\)[^\"]*/\($(basename $h)\"\)#\1\2#" $T/*.h*; done
 sed -i 's/^typedef __hip_internal.*$//' $T/jit.hip && sed -i '1i #include <hip/hip_runtime.h>' $T/jit.hip
 # (the JIT's own options, jit.hip rtc_options: -O1, no contraction, the max-ILP scheduler)
 cd $T && /opt/rocm/bin/hipcc -std=c++17 -O1 --offload-arch=gfx950 -ffp-contract=off -mllvm -amdgpu-sched-strategy=max-ilp --cuda-device-only -S -o $OUT \
