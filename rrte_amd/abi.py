@@ -261,6 +261,23 @@ JIT_EXPORTS = {
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 
+# ------------------------------------------------ march-clip diagnostics (include/rrte_hip_clip.h)
+CLIP_NONE, CLIP_DIFFERENCE, CLIP_INTERSECTION, CLIP_UNION = 0, 1, 2, 4
+
+
+class ClipInfo(C.Structure):
+    """rrte_clip_info: part x is the ball around x_center of radius x_c0 + c1 |(o - x_center).d| + c2 |o|_1."""
+    _fields_ = [("cls", C.c_uint32), ("c1", C.c_float), ("c2", C.c_float), ("a_center", C.c_float * 3),
+                ("a_c0", C.c_float), ("b_center", C.c_float * 3), ("b_c0", C.c_float), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(ClipInfo) == 48
+
+# Every entry point include/rrte_hip_clip.h declares.
+CLIP_EXPORTS = {
+    "rrte_hip_march_clip": (C.c_int, [C.POINTER(SceneIR), C.c_uint32, C.POINTER(ClipInfo)]),
+}
+
 _lib = None
 
 
@@ -282,7 +299,7 @@ def load() -> C.CDLL:
         pass
     lib = C.CDLL(str(LIB_PATH), mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**EXPORTS, **QUERY_EXPORTS, **MESH_EXPORTS, **REFIT_EXPORTS, **BUILD_EXPORTS,
-                               **ACCEL_EXPORTS, **JIT_EXPORTS}.items():
+                               **ACCEL_EXPORTS, **JIT_EXPORTS, **CLIP_EXPORTS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

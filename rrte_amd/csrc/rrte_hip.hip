@@ -28,6 +28,8 @@
 //                     flush_batch, gather_frame, nccl_settle, comm_abort, poll_events, wait_bounded,
 //                     rrte_hip_render_gather* / flush / set_gather_batch / gather_info
 //   fpcheck.hip       rrte_hip_fpcheck
+//   march_clip.hip    rrte_hip_march_clip (the constants of march_clip.hpp, which jit.hip pastes into
+//                     every generated source)
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
