@@ -21,9 +21,9 @@ rrte_status retire(rrte_ctx* c, Retire& r) {
     r.nev = keep;
     for (hipStream_t s : r.streams) {
         if (r.events.size() <= r.nev) {
-            hipEvent_t e = nullptr;
-            HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            r.events.push_back(e);
+            Event e;
+            HIPCHK(c, e.create());
+            r.events.push_back(std::move(e));
         }
         HIPCHK(c, hipEventRecord(r.events[r.nev], s));
         ++r.nev;
@@ -50,14 +50,6 @@ rrte_status wait_retired(rrte_ctx* c, Retire& r) {
     return st;
 }
 
-static void destroy_events(Retire& r) {
-    for (hipEvent_t e : r.events)
-        if (e) (void)hipEventDestroy(e);
-    r.events.clear();
-    r.nev = 0;
-    r.streams.clear();
-}
-
 // RRTE_CSG_GUARDS: unset = 2 (guard operands of >= 2 leaves), 0 = off, N = smallest guarded operand
 uint32_t env_guard_setting() {
     const char* g = getenv("RRTE_CSG_GUARDS");
@@ -67,6 +59,70 @@ uint32_t env_guard_setting() {
 int env_cull_setting() {
     const char* ce = getenv("RRTE_CULL");
     return ce ? (ce[0] != '0' ? 1 : 0) : -1;
+}
+
+// The environment switches of a new context (struct Env): every getenv of context creation.
+Env read_env() {
+    Env e;
+    if (const char* j = getenv("RRTE_JIT")) e.jit_mode = (int)strtol(j, nullptr, 0);
+    if (const char* d = getenv("RRTE_DEBUG")) e.debug = (uint32_t)strtoul(d, nullptr, 0);
+    e.cull = env_cull_setting();
+    if (const char* t = getenv("RRTE_TILE_CULL")) e.tile_cull = t[0] != '0';
+    if (const char* t = getenv("RRTE_JIT_PLAIN")) e.jit_plain = t[0] != '0';
+    if (const char* g = getenv("RRTE_FORCE_GATHER")) e.force_gather = g[0] == '1';
+    if (const char* g = getenv("RRTE_HOST_PROFILE")) e.host_prof = g[0] == '1';
+    if (const char* g = getenv("RRTE_MESH_BUILD")) {
+        if (!strcmp(g, "device")) e.mesh_build = RRTE_MESH_BUILD_DEVICE;
+        else if (!strcmp(g, "host")) e.mesh_build = RRTE_MESH_BUILD_HOST;
+    }
+    if (const char* g = getenv("RRTE_SCENE_ACCEL")) {
+        if (!strcmp(g, "on")) e.accel_policy = RRTE_SCENE_ACCEL_ON;
+        else if (!strcmp(g, "off")) e.accel_policy = RRTE_SCENE_ACCEL_OFF;
+    }
+    if (const char* g = getenv("RRTE_SCENE_ACCEL_MIN"); g && *g)
+        if (const uint32_t m = (uint32_t)strtoul(g, nullptr, 0)) e.accel_min = m;
+    if (const char* g = getenv("RRTE_TRACE")) e.trace = g[0] == '1';
+    if (const char* g = getenv("RRTE_DIAG_SKIP")) e.diag_skip = (uint32_t)strtoul(g, nullptr, 0);
+    if (const char* g = getenv("RRTE_GATHER_RGB24")) e.gather_rgba = g[0] == '0';
+    e.guard_leaves = env_guard_setting();
+    if (const char* g = getenv("RRTE_COMM_TIMEOUT_MS")) e.comm_timeout_ms = std::max<uint32_t>(1u, (uint32_t)strtoul(g, nullptr, 0));
+    if (const char* g = getenv("RRTE_FAULT_STALL_GATHER")) e.fault_stall_at = strtoull(g, nullptr, 0);
+    if (const char* g = getenv("RRTE_BATCH_SLABS"); g && *g)
+        e.batch_slabs = std::max(1, std::min(rrte_ctx::kBatchSlabs, (int)strtol(g, nullptr, 0)));
+    if (const char* g = getenv("RRTE_GATHER_SELF")) e.gather_self = g[0] == '1';
+    if (const char* g = getenv("RRTE_BAND_SKY")) e.band_sky = g[0] != '0';
+    if (const char* g = getenv("RRTE_COMM_PRIORITY")) e.comm_priority = g[0] != '0';
+    if (const char* g = getenv("RRTE_GENERIC_ALL")) e.generic_all = g[0] == '1';
+    if (const char* g = getenv("RRTE_GUARD_POLICY"); g && *g) e.guard_policy = std::min(2, std::max(0, atoi(g)));
+    if (const char* g = getenv("RRTE_BATCH_LAUNCH")) e.batch_launch = g[0] != '0';
+    if (const char* g = getenv("RRTE_BND_ZEROCOPY")) e.bnd_zerocopy = g[0] != '0';
+    if (const char* g = getenv("RRTE_ZC_TILE_SHIFT"))
+        e.zc_tile_shift = std::max(3u, std::min(6u, (uint32_t)strtoul(g, nullptr, 0)));
+    if (const char* g = getenv("RRTE_ZC_SYSTEM_STORE")) e.zc_system_store = g[0] != '0';
+    if (const char* g = getenv("RRTE_NOCOMM_WAIT_MS")) e.nocomm_wait_ms = (uint32_t)strtoul(g, nullptr, 0);
+    if (const char* g = getenv("RRTE_TILE_ORDER")) {
+        e.tile_order = g[0] != '0';
+        e.tile_order_fixed = g[0] == '2';  // 0 image order, 2 fixed permutation (tests), else measured (default)
+    }
+    if (const char* g = getenv("RRTE_TEST_RECYCLE")) e.test_recycle = g[0] == '1';
+    if (const char* g = getenv("RRTE_FAULT_BAD_SLOT")) e.fault_bad_slot = (g[0] == '1' || g[0] == '2') ? g[0] - '0' : 0;
+    if (const char* g = getenv("RRTE_DUMP_SCENE"); g && *g) e.dump_path = g;
+    if (const char* g = getenv("RRTE_BND_CHUNKS"); g && *g)
+        e.bnd_chunks = std::max(1, std::min(rrte_ctx::kBndChunksMax, (int)strtol(g, nullptr, 0)));
+    if (const char* t = getenv("RRTE_JIT_TOPO"); t && *t) e.jit_topo = (int)strtol(t, nullptr, 0);
+    if (const char* g = getenv("RRTE_EMULATE_PEERS")) {
+        const int n = (int)strtol(g, nullptr, 0);
+        if (n > 1) e.emu_peers = n;
+    }
+    if (const char* g = getenv("RRTE_EMULATE_RANK")) {
+        int n = 0, r = 0;
+        if (sscanf(g, "%d:%d", &n, &r) == 2 && n > 1 && r >= 0 && r < n) {
+            e.emu_nranks = n;
+            e.emu_rank = r;
+        }
+    }
+    if (const char* g = getenv("RRTE_HOST_REGISTER_FLAGS")) e.host_register_flags = (unsigned)strtoul(g, nullptr, 0);  // (A/B)
+    return e;
 }
 
 }  // namespace rrte
@@ -81,66 +137,9 @@ rrte_status rrte_hip_create(int device, rrte_ctx** out) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return RRTE_NO_DEVICE;
     if (device < 0 || device >= n) return RRTE_NO_DEVICE;
-    rrte_ctx* c = new (std::nothrow) rrte_ctx();
+    rrte_ctx* c = new (std::nothrow) rrte_ctx(read_env());
     if (!c) return RRTE_HIP_ERROR;
     c->device = device;
-    if (const char* j = getenv("RRTE_JIT")) c->jit_mode = (int)strtol(j, nullptr, 0);
-    if (const char* d = getenv("RRTE_DEBUG")) c->env_debug = (uint32_t)strtoul(d, nullptr, 0);
-    c->env_cull = env_cull_setting();
-    if (const char* t = getenv("RRTE_TILE_CULL")) c->env_tile_cull = t[0] != '0';
-    if (const char* t = getenv("RRTE_JIT_PLAIN")) c->env_jit_plain = t[0] != '0';
-    if (const char* g = getenv("RRTE_FORCE_GATHER")) c->env_force_gather = g[0] == '1';
-    if (const char* g = getenv("RRTE_HOST_PROFILE")) c->host_prof = g[0] == '1';
-    if (const char* g = getenv("RRTE_MESH_BUILD")) {
-        if (!strcmp(g, "device")) c->mesh_build = RRTE_MESH_BUILD_DEVICE;
-        else if (!strcmp(g, "host")) c->mesh_build = RRTE_MESH_BUILD_HOST;
-    }
-    if (const char* g = getenv("RRTE_SCENE_ACCEL")) {
-        if (!strcmp(g, "on")) c->accel_policy = RRTE_SCENE_ACCEL_ON;
-        else if (!strcmp(g, "off")) c->accel_policy = RRTE_SCENE_ACCEL_OFF;
-    }
-    if (const char* g = getenv("RRTE_SCENE_ACCEL_MIN"); g && *g)
-        if (const uint32_t m = (uint32_t)strtoul(g, nullptr, 0)) c->accel_min = m;
-    if (const char* g = getenv("RRTE_TRACE")) c->trace = g[0] == '1';
-    if (const char* g = getenv("RRTE_DIAG_SKIP")) c->env_diag_skip = (uint32_t)strtoul(g, nullptr, 0);
-    if (const char* g = getenv("RRTE_GATHER_RGB24")) c->env_gather_rgba = g[0] == '0';
-    c->env_guard_leaves = env_guard_setting();
-    if (const char* g = getenv("RRTE_COMM_TIMEOUT_MS")) c->comm_timeout_ms = std::max<uint32_t>(1u, (uint32_t)strtoul(g, nullptr, 0));
-    if (const char* g = getenv("RRTE_FAULT_STALL_GATHER")) c->fault_stall_at = strtoull(g, nullptr, 0);
-    if (const char* g = getenv("RRTE_BATCH_SLABS"); g && *g)
-        c->batch_slabs = std::max(1, std::min(rrte_ctx::kBatchSlabs, (int)strtol(g, nullptr, 0)));
-    if (const char* g = getenv("RRTE_GATHER_SELF")) c->env_gather_self = g[0] == '1';
-    if (const char* g = getenv("RRTE_BAND_SKY")) c->env_band_sky = g[0] != '0';
-    if (const char* g = getenv("RRTE_COMM_PRIORITY")) c->env_comm_priority = g[0] != '0';
-    if (const char* g = getenv("RRTE_GENERIC_ALL")) c->env_generic_all = g[0] == '1';
-    if (const char* g = getenv("RRTE_GUARD_POLICY"); g && *g) c->env_guard_policy = std::min(2, std::max(0, atoi(g)));
-    if (const char* g = getenv("RRTE_BATCH_LAUNCH")) c->env_batch_launch = g[0] != '0';
-    if (const char* g = getenv("RRTE_BND_ZEROCOPY")) c->env_bnd_zerocopy = g[0] != '0';
-    if (const char* g = getenv("RRTE_ZC_TILE_SHIFT"))
-        c->zc_tile_shift = std::max(3u, std::min(6u, (uint32_t)strtoul(g, nullptr, 0)));
-    if (const char* g = getenv("RRTE_ZC_SYSTEM_STORE")) c->env_zc_system_store = g[0] != '0';
-    if (const char* g = getenv("RRTE_NOCOMM_WAIT_MS")) c->env_nocomm_wait_ms = (uint32_t)strtoul(g, nullptr, 0);
-    if (const char* g = getenv("RRTE_TILE_ORDER")) {
-        c->env_tile_order = g[0] != '0';
-        c->env_tile_order_fixed = g[0] == '2';  // 0 image order, 2 fixed permutation (tests), else measured (default)
-    }
-    if (const char* g = getenv("RRTE_TEST_RECYCLE")) c->env_test_recycle = g[0] == '1';
-    if (const char* g = getenv("RRTE_FAULT_BAD_SLOT")) c->env_fault_bad_slot = (g[0] == '1' || g[0] == '2') ? g[0] - '0' : 0;
-    if (const char* g = getenv("RRTE_DUMP_SCENE"); g && *g) c->dump_path = g;
-    if (const char* g = getenv("RRTE_BND_CHUNKS"); g && *g)
-        c->bnd_chunks = std::max(1, std::min(rrte_ctx::kBndChunksMax, (int)strtol(g, nullptr, 0)));
-    if (const char* t = getenv("RRTE_JIT_TOPO"); t && *t) c->env_jit_topo = (int)strtol(t, nullptr, 0);
-    if (const char* e = getenv("RRTE_EMULATE_PEERS")) {
-        const int n = (int)strtol(e, nullptr, 0);
-        if (n > 1) c->emu_peers = n;
-    }
-    if (const char* e = getenv("RRTE_EMULATE_RANK")) {
-        int n = 0, r = 0;
-        if (sscanf(e, "%d:%d", &n, &r) == 2 && n > 1 && r >= 0 && r < n) {
-            c->emu_nranks = n;
-            c->emu_rank = r;
-        }
-    }
     auto bail = [&](hipError_t e) {
         (void)e;
         rrte_hip_destroy(c);
@@ -148,26 +147,26 @@ rrte_status rrte_hip_create(int device, rrte_ctx** out) {
     };
     hipError_t e;
     if ((e = hipSetDevice(device)) != hipSuccess) return bail(e);
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e);
-    if ((e = hipEventCreate(&c->ev0)) != hipSuccess) return bail(e);
-    if ((e = hipEventCreate(&c->ev1)) != hipSuccess) return bail(e);
-    if ((e = hipEventCreate(&c->ev2)) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_counters), kCounterBytes)) != hipSuccess) return bail(e);
+    if ((e = c->stream.create()) != hipSuccess) return bail(e);
+    if ((e = c->ev0.create(true)) != hipSuccess) return bail(e);
+    if ((e = c->ev1.create(true)) != hipSuccess) return bail(e);
+    if ((e = c->ev2.create(true)) != hipSuccess) return bail(e);
+    if ((e = c->d_counters.alloc(kCounterShards * kCounterStride)) != hipSuccess) return bail(e);
     // (on the context's stream: its first operation sets up its hardware queue, here and not in a frame)
     if ((e = hipMemsetAsync(c->d_counters, 0, kCounterBytes, c->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess)
         return bail(e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->h_counters), kCounterBytes, hipHostMallocDefault)) != hipSuccess) return bail(e);
+    if ((e = c->h_counters.alloc(kCounterShards * kCounterStride)) != hipSuccess) return bail(e);
     memset(c->h_counters, 0, kCounterBytes);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->h_counters2), kCounterBytes, hipHostMallocDefault)) != hipSuccess) return bail(e);
+    if ((e = c->h_counters2.alloc(kCounterShards * kCounterStride)) != hipSuccess) return bail(e);
     memset(c->h_counters2, 0, kCounterBytes);
-    for (hipEvent_t& ev : c->ev_ctr)
-        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail(e);
-    if ((e = hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming)) != hipSuccess) return bail(e);
+    for (Version& v : c->ctr)
+        if ((e = v.ev_up.create()) != hipSuccess) return bail(e);
+    if ((e = c->ev_done.create()) != hipSuccess) return bail(e);
     // the upload stream, and a first copy of a tile list's size class through it: the runtime sets up
     // what such a copy needs at its first use (7-8 ms measured, inside the first frame of a new launch
     // shape: profiles/r06_engine_loop_trace.log) -- here rather than in a frame
-    if ((e = hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e);
+    if ((e = c->upload_stream.create()) != hipSuccess) return bail(e);
     {
         // the library's code objects of the frame paths (every generic kernel; the gather's expansion):
         // the runtime loads one at the first use of a kernel in it -- ~20 ms inside the first frame
@@ -178,20 +177,20 @@ rrte_status rrte_hip_create(int device, rrte_ctx** out) {
     {
         constexpr size_t kWarm = 129600;  // a 1080p frame's list (32400 slots)
         // (the buffers are freed with the context: a free here could wait for other contexts' frames)
-        if ((e = hipHostMalloc(&c->h_warm, kWarm, hipHostMallocDefault)) != hipSuccess) return bail(e);
+        if ((e = c->h_warm.alloc(kWarm)) != hipSuccess) return bail(e);
         memset(c->h_warm, 0, kWarm);
         // (and the way back on the context's stream: a frame's tile-profile copy is a D2H of that size)
-        if ((e = hipMalloc(&c->d_warm, kWarm)) != hipSuccess ||
+        if ((e = c->d_warm.alloc(kWarm)) != hipSuccess ||
             (e = hipMemcpyAsync(c->d_warm, c->h_warm, kWarm, hipMemcpyHostToDevice, c->upload_stream)) != hipSuccess ||
             (e = hipStreamSynchronize(c->upload_stream)) != hipSuccess ||
             (e = hipMemcpyAsync(c->h_warm, c->d_warm, kWarm, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
             (e = hipStreamSynchronize(c->stream)) != hipSuccess)
             return bail(e);
     }
-    if (c->fault_stall_at) {
-        if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->h_stall), 64, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess)
+    if (c->env.fault_stall_at) {
+        if ((e = c->h_stall.alloc(16, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess)
             return bail(e);
-        *c->h_stall = 1u;
+        *c->h_stall.get() = 1u;
     }
     *out = c;
     return RRTE_OK;
@@ -199,39 +198,39 @@ rrte_status rrte_hip_create(int device, rrte_ctx** out) {
 
 void rrte_hip_destroy(rrte_ctx* c) {
     if (!c) return;
-    if (c->host_prof && c->hp_frames) {
+    if (c->env.host_prof && c->hp_frames) {
         static const char* names[9] = {"validate", "upload_check", "slab_setup", "render_launch", "event_chain",
                                        "ncclGather", "deinterleave", "event_record", "(of render_launch: the launch call)"};
         fprintf(stderr, "rrte host profile (%llu gather frames, us/frame):", (unsigned long long)c->hp_frames);
         for (int i = 0; i < 9; ++i) fprintf(stderr, " %s %.2f", names[i], c->hp[i] / (double)c->hp_frames);
         fprintf(stderr, "\n");
     }
-    if (c->host_prof && c->hpa_frames) {
+    if (c->env.host_prof && c->hpa_frames) {
         static const char* names[5] = {"validate", "scene_check", "plan", "tile_order+jit", "launch_call"};
         fprintf(stderr, "rrte host profile (%llu async frames, us/frame):", (unsigned long long)c->hpa_frames);
         for (int i = 0; i < 5; ++i) fprintf(stderr, " %s %.2f", names[i], c->hp[10 + i] / (double)c->hpa_frames);
         fprintf(stderr, "\n");
     }
-    if (c->host_prof && c->hpu_n) {
+    if (c->env.host_prof && c->hpu_n) {
         static const char* names[9] = {"lower", "mesh_bvh", "csg_guards", "topology", "version_wait", "staging",
                                        "copy_call", "event_record", "bookkeeping"};
         fprintf(stderr, "rrte host profile (%llu scene uploads, us/upload):", (unsigned long long)c->hpu_n);
         for (int i = 0; i < 9; ++i) fprintf(stderr, " %s %.2f", names[i], c->hpu[i] / (double)c->hpu_n);
         fprintf(stderr, "\n");
     }
-    if (c->host_prof && c->build_times.n) {
+    if (c->env.host_prof && c->build_times.n) {
         const BuildTimes& bt = c->build_times;
         const double n = (double)bt.n;
         fprintf(stderr, "rrte host profile (%llu device mesh builds, us/build): host_scan %.2f enqueue %.2f depth_wait %.2f "
                         "boxes_enqueue %.2f readback %.2f\n",
                 (unsigned long long)bt.n, bt.host_scan / n, bt.enqueue / n, bt.depth_wait / n, bt.boxes_enqueue / n, bt.readback / n);
     }
-    if (c->trace) {
+    if (c->env.trace) {
         for (const auto& t : c->trace_log)
             fprintf(stderr, "rrte trace %12.1f us  %-34s stream %p event %p  %u %u\n", t.us, t.what, t.st, t.ev, t.a, t.b);
     }
     (void)hipSetDevice(c->device);
-    if (c->h_stall) __hip_atomic_store(c->h_stall, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // injected stall
+    if (c->h_stall) __hip_atomic_store(c->h_stall.get(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // injected stall
     // gathers first, bounded (a dead peer aborts the communicator instead of hanging here); then the
     // frames that may still run on caller streams
     if (c->comm && wait_bounded(c) != RRTE_OK) c->comm = nullptr;  // (comm_abort has aborted it)
@@ -239,71 +238,10 @@ void rrte_hip_destroy(rrte_ctx* c) {
     if (c->comm) ncclCommDestroy(c->comm);
     for (const auto& hr : c->host_regs) (void)hipHostUnregister(hr.p);
     c->jit_pending.clear();  // joins background compiles
+    for (auto& tp : c->tprof)
+        if (tp.working) tp.work.wait();  // the tile-order workers
     for (auto& kv : c->jit_cache) jit_release(kv.second);
-    for (auto& B : c->sb) {
-        if (B.d_buf) (void)hipFree(B.d_buf);
-        if (B.h_stage) (void)hipHostFree(B.h_stage);
-        if (B.ev_up) (void)hipEventDestroy(B.ev_up);
-        destroy_events(B.ret);
-    }
-    void* bufs[] = {c->d_rgba, c->d_f32, c->d_counters, c->d_gather, c->d_full, c->d_qin, c->d_qout, c->d_build};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (void* b : c->graveyard)
-        if (b) (void)hipFree(b);
-    destroy_events(c->launched);
-    for (uint32_t* b : c->d_slab)
-        if (b) (void)hipFree(b);
-    if (c->h_counters) (void)hipHostFree(c->h_counters);
-    if (c->h_counters2) (void)hipHostFree(c->h_counters2);
-    if (c->h_warm) (void)hipHostFree(c->h_warm);
-    if (c->d_warm) (void)hipFree(c->d_warm);
-    for (hipEvent_t e : c->ev_ctr)
-        if (e) (void)hipEventDestroy(e);
-    if (c->ev_done) (void)hipEventDestroy(c->ev_done);
-    if (c->ev_accel) (void)hipEventDestroy(c->ev_accel);
-    if (c->h_stall) (void)hipHostFree(c->h_stall);
-    for (auto& tp : c->tprof) {
-        if (tp.working) tp.work.wait();
-        if (tp.d_cost) (void)hipFree(tp.d_cost);
-        if (tp.h_cost) (void)hipHostFree(tp.h_cost);
-        if (tp.ev) (void)hipEventDestroy(tp.ev);
-        for (int i = 0; i < rrte_ctx::TileProfile::kVersions; ++i) {
-            if (tp.d_list[i]) (void)hipFree(tp.d_list[i]);
-            destroy_events(tp.ret[i]);
-        }
-        if (tp.h_arena) (void)hipHostFree(tp.h_arena);
-        for (hipEvent_t e : tp.ev_up)
-            if (e) (void)hipEventDestroy(e);
-    }
-    for (int i = 0; i < rrte_ctx::kBndChunksMax; ++i) {
-        if (c->bnd_stream[i]) (void)hipStreamDestroy(c->bnd_stream[i]);
-        if (c->ev_bchunk[i]) (void)hipEventDestroy(c->ev_bchunk[i]);
-    }
-    if (c->bnd_copy) (void)hipStreamDestroy(c->bnd_copy);
-    if (c->ev_bcopy) (void)hipEventDestroy(c->ev_bcopy);
-    if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
-    for (hipEvent_t e : c->ev_poll)
-        if (e) (void)hipEventDestroy(e);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->ev2) (void)hipEventDestroy(c->ev2);
-    for (hipEvent_t e : c->ev_gath)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_batch)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_render)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->batch.ev_src)
-        if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < rrte_ctx::kBatchSlabs; ++i) {
-        if (c->d_bsend[i]) (void)hipFree(c->d_bsend[i]);
-        if (c->d_brecv[i]) (void)hipFree(c->d_brecv[i]);
-        if (c->render_stream[i]) (void)hipStreamDestroy(c->render_stream[i]);
-    }
-    if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // every buffer, event and stream: the members' destructors (resources.hpp)
 }
 
 const char* rrte_hip_last_error(const rrte_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -319,8 +257,6 @@ rrte_status rrte_hip_synchronize(rrte_ctx* c) {
     if ((r = retire(c, c->launched)) != RRTE_OK || (r = wait_retired(c, c->launched)) != RRTE_OK) return r;
     HIPCHK(c, hipDeviceSynchronize());
     // idle: buffers replaced while frames were in flight can go, and every retired version is free
-    for (void* b : c->graveyard)
-        if (b) (void)hipFree(b);
     c->graveyard.clear();
     return finish_frame(c);
 }
@@ -471,9 +407,7 @@ rrte_status rrte_hip_stats(rrte_ctx* c, rrte_stats* out) {
 rrte_status rrte_hip_host_register(rrte_ctx* c, void* host, size_t bytes) {
     if (!c || !host || bytes == 0) return fail(c, RRTE_INVALID_ARG, "null or empty host range");
     HIPCHK(c, hipSetDevice(c->device));
-    unsigned flags = hipHostRegisterMapped;
-    if (const char* g = getenv("RRTE_HOST_REGISTER_FLAGS")) flags = (unsigned)strtoul(g, nullptr, 0);  // (A/B)
-    HIPCHK(c, hipHostRegister(host, bytes, flags));
+    HIPCHK(c, hipHostRegister(host, bytes, c->env.host_register_flags));
     c->host_regs.push_back({host, bytes});
     return RRTE_OK;
 }

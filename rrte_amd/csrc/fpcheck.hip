@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "pixel_encode.hpp"
+#include "resources.hpp"
 
 using namespace rrte;
 
@@ -48,8 +49,9 @@ rrte_status rrte_hip_fpcheck(int device, int kind, uint64_t lo, uint64_t hi, uin
         hi > (kind == RRTE_FPCHECK_DIV ? (1ull << 23) : (1ull << 32)))
         return RRTE_INVALID_ARG;
     if (hipSetDevice(device) != hipSuccess) return RRTE_HIP_ERROR;
-    unsigned long long* d = nullptr;
-    if (hipMalloc(&d, sizeof(unsigned long long)) != hipSuccess) return RRTE_HIP_ERROR;
+    DeviceBuf<unsigned long long> buf;  // (released on every return)
+    if (buf.alloc(1) != hipSuccess) return RRTE_HIP_ERROR;
+    unsigned long long* const d = buf;
     bool ok = hipMemset(d, 0, sizeof(unsigned long long)) == hipSuccess;
     if (kind == RRTE_FPCHECK_DIV) {
         const uint64_t chunk = 1u << 14;  // b significands per launch (one workgroup each)
@@ -70,7 +72,6 @@ rrte_status rrte_hip_fpcheck(int device, int kind, uint64_t lo, uint64_t hi, uin
     unsigned long long h = 0;
     ok = ok && hipDeviceSynchronize() == hipSuccess &&
          hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(d);
     if (!ok) return RRTE_HIP_ERROR;
     *mismatches = h;
     return RRTE_OK;

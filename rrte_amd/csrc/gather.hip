@@ -101,7 +101,7 @@ static_assert(rrte_ctx::kMaxBatch == sizeof(DeinterleaveTargets::full) / sizeof(
 // test is on signs only (no host arithmetic to mirror); NaN fails it.  Every rank decides from the
 // same scene and parameters, so all agree on the slab format.  RRTE_GATHER_RGB24=0 forces RGBA8.
 static bool slab_rgb24(const rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_params* p) {
-    if (c->env_gather_rgba || (c->env_debug & ~4u) || p->mode != RRTE_MODE_LAMBERT_SHADOW) return false;
+    if (c->env.gather_rgba || (c->env.debug & ~4u) || p->mode != RRTE_MODE_LAMBERT_SHADOW) return false;
     const float thr = p->samples_per_pixel == 1 ? 0.0f : 1.0f;
     if (!(p->background[3] >= thr)) return false;
     for (uint32_t i = 0; i < s->num_materials; ++i)
@@ -179,7 +179,7 @@ rrte_status render_batch(rrte_ctx* c, bool at_flush) {
     hipStream_t rs = c->render_stream[k];
     // the renders follow the frames' caller streams (scene uploads, the callers' own prior work) and
     // the slab's previous batch (its gather reads the send slab)
-    if (!(c->env_diag_skip & 4u))
+    if (!(c->env.diag_skip & 4u))
         for (uint32_t i = 0; i < b.nsrc; ++i) {
             HIPCHK(c, ev_record(c, b.ev_src[i], b.src[i], "record src (render)"));
             HIPCHK(c, ev_wait(c, rs, b.ev_src[i], "render waits src"));
@@ -210,14 +210,14 @@ rrte_status render_batch(rrte_ctx* c, bool at_flush) {
 // Before a collective on `st`: count it, and enqueue the injected stall if this is the one.
 static rrte_status before_collective(rrte_ctx* c, hipStream_t st) {
     ++c->gathers_issued;
-    if (c->fault_stall_at && c->gathers_issued == c->fault_stall_at && c->h_stall) {
-        __hip_atomic_store(c->h_stall, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (c->env.fault_stall_at && !c->stall_fired && c->gathers_issued == c->env.fault_stall_at && c->h_stall) {
+        __hip_atomic_store(c->h_stall.get(), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         uint32_t* dflag = nullptr;
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&dflag), c->h_stall, 0));
+        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&dflag), c->h_stall.get(), 0));
         hipLaunchKernelGGL(stall_kernel, dim3(1), dim3(64), 0, st, dflag);
         HIPCHK(c, hipGetLastError());
         c->stall_armed = true;
-        c->fault_stall_at = 0;  // one-shot
+        c->stall_fired = true;  // one-shot
     }
     return RRTE_OK;
 }
@@ -246,12 +246,12 @@ rrte_status nccl_settle(rrte_ctx* c, ncclResult_t r, const char* what) {
 // bounded chance to drain (so nothing of this communicator is still running when it is torn down),
 // abort the communicator and fail every later gather call until rrte_hip_comm_init.
 static rrte_status comm_abort(rrte_ctx* c, const char* why) {
-    if (c->stall_armed && c->h_stall) __hip_atomic_store(c->h_stall, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (c->stall_armed && c->h_stall) __hip_atomic_store(c->h_stall.get(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     c->stall_armed = false;
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
         bool busy = false;
-        for (hipEvent_t e : c->ev_poll)
+        for (const Event& e : c->ev_poll)
             if (e && hipEventQuery(e) == hipErrorNotReady) busy = true;
         if (!busy || std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2000)) break;
         std::this_thread::sleep_for(std::chrono::microseconds(100));
@@ -274,9 +274,9 @@ static rrte_status comm_abort(rrte_ctx* c, const char* why) {
 // down), so the wait lasts as long as the device needs up to RRTE_NOCOMM_WAIT_MS (default 10 minutes,
 // far above any queue of frames; RRTE_HIP_ERROR after it so a hung or faulted kernel still returns;
 // 0 = no limit).
-rrte_status poll_events(rrte_ctx* c, const hipEvent_t* ev, size_t n) {
+rrte_status poll_events(rrte_ctx* c, const Event* ev, size_t n) {
     const auto t0 = std::chrono::steady_clock::now();
-    const uint32_t limit_ms = c->comm ? c->comm_timeout_ms : c->env_nocomm_wait_ms;
+    const uint32_t limit_ms = c->comm ? c->comm_timeout_ms : c->env.nocomm_wait_ms;
     for (uint32_t spin = 0;; ++spin) {
         bool busy = false;
         for (size_t i = 0; i < n; ++i) {
@@ -317,7 +317,7 @@ rrte_status wait_bounded(rrte_ctx* c) {
     size_t n = 0;
     for (int i = 0; i < kPoll; ++i) {
         if (!ss[i]) continue;
-        if (!c->ev_poll[n]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_poll[n], hipEventDisableTiming));
+        HIPCHK(c, c->ev_poll[n].create());
         HIPCHK(c, hipEventRecord(c->ev_poll[n], ss[i]));
         ++n;
     }
@@ -360,7 +360,7 @@ static rrte_status flush_batch(rrte_ctx* c) {
         // a 1-rank communicator (emulated ranks, RRTE_EMULATE_RANK) there is no peer, RRTE_GATHER_SELF
         // routes the root's bands through RCCL to itself
         const bool self_only = c->comm_size == 1;  // (no real peer: only the root's RRTE_GATHER_SELF round trip)
-        if (!(c->env_diag_skip & 1u) && (!self_only || (!b.in_place && c->rank == b.root))) {
+        if (!(c->env.diag_skip & 1u) && (!self_only || (!b.in_place && c->rank == b.root))) {
             // (a failing call inside the group still closes it before the error is returned, so the
             // thread's group depth is balanced when comm_abort tears the communicator down)
             NCCLCHK(c, ncclGroupStart());
@@ -380,11 +380,11 @@ static rrte_status flush_batch(rrte_ctx* c) {
                 return fail(c, RRTE_RCCL_ERROR, "%s failed: %s", what, ncclGetErrorString(gr));
             NCCLCHK(c, er);
         }
-        if (self_only && c->emu_peers > 1 && c->rank == b.root &&
+        if (self_only && c->env.emu_peers > 1 && c->rank == b.root &&
             (r = render_peers(c, b.plan, b.cam, b.n, c->d_brecv[k], count, b.slice, b.root, c->comm_stream)) != RRTE_OK)
             return r;
         hs.lap(5);
-        if (c->rank == b.root && !(c->env_diag_skip & 2u) && (c->nranks > 1 || !b.in_place)) {
+        if (c->rank == b.root && !(c->env.diag_skip & 2u) && (c->nranks > 1 || !b.in_place)) {
             DeinterleaveTargets t{};
             for (uint32_t j = 0; j < b.n; ++j) t.full[j] = b.full[j];
             if ((r = deinterleave(c, c->comm_stream, c->d_brecv[k], t, b.n, b.width, b.height, b.bm, b.rgb24, count,
@@ -398,7 +398,7 @@ static rrte_status flush_batch(rrte_ctx* c) {
     if ((r = issue()) != RRTE_OK) return comm_abort(c, ("batch gather failed: " + c->err).c_str());
     c->last_gather_stream = c->comm_stream;
     c->last_gather_ev = c->ev_batch[k];
-    c->bslot = (k + 1) % c->batch_slabs;
+    c->bslot = (k + 1) % c->env.batch_slabs;
     b.n = b.nsrc = b.rendered = 0;
     hs.lap(7);
     return RRTE_OK;
@@ -445,7 +445,7 @@ static rrte_status gather_frame(rrte_ctx* c, const rrte_scene_ir* s, const rrte_
     if (c->comm_failed)
         return fail(c, RRTE_RCCL_ERROR, "communicator aborted earlier (%s); call rrte_hip_comm_init", c->comm_fail_msg.c_str());
     // one rank: no exchange (RRTE_FORCE_GATHER=1 still takes the gather path: tests on one GPU)
-    if (c->nranks == 1 && !(c->env_force_gather && c->comm)) {
+    if (c->nranks == 1 && !(c->env.force_gather && c->comm)) {
         r = launch(c, s, p, p->height, static_cast<uint32_t*>(d_full), nullptr, st);
         if (r == RRTE_OK) c->pending_primary = (uint64_t)p->width * p->height * p->samples_per_pixel;
         if (timing) HIPCHK(c, hipEventRecord(c->ev1, st));
@@ -460,22 +460,22 @@ static rrte_status gather_frame(rrte_ctx* c, const rrte_scene_ir* s, const rrte_
             // (RRTE_COMM_PRIORITY=0: default priority, A/B)
             int lo = 0, hi = 0;
             HIPCHK(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
-            HIPCHK(c, hipStreamCreateWithPriority(&c->comm_stream, hipStreamNonBlocking, c->env_comm_priority ? hi : lo));
-            for (int i = 0; i < c->batch_slabs; ++i) {  // (only the slots of the ring in use)
-                HIPCHK(c, hipStreamCreateWithFlags(&c->render_stream[i], hipStreamNonBlocking));
-                HIPCHK(c, hipEventCreateWithFlags(&c->ev_batch[i], hipEventDisableTiming));
-                HIPCHK(c, hipEventCreateWithFlags(&c->ev_render[i], hipEventDisableTiming));
+            HIPCHK(c, c->comm_stream.create(c->env.comm_priority ? hi : lo));
+            for (int i = 0; i < c->env.batch_slabs; ++i) {  // (only the slots of the ring in use)
+                HIPCHK(c, c->render_stream[i].create());
+                HIPCHK(c, c->ev_batch[i].create());
+                HIPCHK(c, c->ev_render[i].create());
             }
             // one empty kernel on each new stream now: the runtime binds a stream to a hardware queue at
             // its first dispatch, which must not happen inside a later frame's critical path
-            for (int i = 0; i < c->batch_slabs; ++i) {
+            for (int i = 0; i < c->env.batch_slabs; ++i) {
                 hipLaunchKernelGGL(noop_kernel, dim3(1), dim3(64), 0, c->render_stream[i]);
                 HIPCHK(c, hipGetLastError());
             }
             hipLaunchKernelGGL(noop_kernel, dim3(1), dim3(64), 0, c->comm_stream);
             HIPCHK(c, hipGetLastError());
             for (int i = 0; i < rrte_ctx::kMaxBatch; ++i)
-                HIPCHK(c, hipEventCreateWithFlags(&b.ev_src[i], hipEventDisableTiming));
+                HIPCHK(c, b.ev_src[i].create());
         }
         LaunchPlan L = plan_launch(c, s, &pp, rows, kflags, 0u, &bm);
         // a frame of another size, band, root, slab format or render setup closes the open batch
@@ -495,17 +495,17 @@ static rrte_status gather_frame(rrte_ctx* c, const rrte_scene_ir* s, const rrte_
             b.slice = slice;
             b.bm = bm;
             b.plan = L;
-            b.in_place = c->rank == root && !c->env_gather_self;
-            b.per_frame = !c->env_batch_launch;
+            b.in_place = c->rank == root && !c->env.gather_self;
+            b.per_frame = !c->env.batch_launch;
             // every rank holds a receive slab too (the root's is the only one written)
             const size_t send = (size_t)b.cap * slice, recv = send * (size_t)c->nranks;
-            if (c->cap_bsend[k] < send || c->cap_brecv[k] < recv) {
+            if (c->d_bsend[k].cap() < send || c->d_brecv[k].cap() < recv) {
                 // every slab of the ring in use at once (at the first batch: none is allocated inside a
                 // later timed batch); a smaller slab an in-flight gather may still use goes to the
                 // graveyard (freed when the context is next idle), so nothing waits for the device here
-                for (int q = 0; q < c->batch_slabs; ++q) {
-                    if ((r = ensure(c, c->d_bsend[q], c->cap_bsend[q], send)) != RRTE_OK) return r;
-                    if ((r = ensure(c, c->d_brecv[q], c->cap_brecv[q], recv)) != RRTE_OK) return r;
+                for (int q = 0; q < c->env.batch_slabs; ++q) {
+                    if ((r = ensure(c, c->d_bsend[q], send)) != RRTE_OK) return r;
+                    if ((r = ensure(c, c->d_brecv[q], recv)) != RRTE_OK) return r;
                 }
             }
         }
@@ -540,25 +540,25 @@ static rrte_status gather_frame(rrte_ctx* c, const rrte_scene_ir* s, const rrte_
         if ((r = flush_batch(c)) != RRTE_OK) return r;  // keep every rank's collectives in issue order
         if (!c->ev_gath[0])
             for (int i = 0; i < rrte_ctx::kSlabs; ++i)
-                HIPCHK(c, hipEventCreateWithFlags(&c->ev_gath[i], hipEventDisableTiming));
+                HIPCHK(c, c->ev_gath[i].create());
         // slabs are a ring shared by every frame in flight: a frame on another stream than the slab's
         // previous user waits until that frame has been gathered (same stream: stream order suffices)
         const int slot = (int)(c->gather_frames % rrte_ctx::kSlabs);
         const size_t slab_words = slice * (size_t)c->nranks / 4u;
-        if (c->cap_slab[slot] < slab_words) {
+        if (c->d_slab[slot].cap() < slab_words) {
             // (re)size the whole ring at once; smaller slabs in-flight gathers may still use go to the
             // graveyard (freed when the context is next idle): no device synchronisation
             for (int i = 0; i < rrte_ctx::kSlabs; ++i)
-                if ((r = ensure(c, c->d_slab[i], c->cap_slab[i], slab_words)) != RRTE_OK) return r;
+                if ((r = ensure(c, c->d_slab[i], slab_words)) != RRTE_OK) return r;
         }
-        uint8_t* slab = reinterpret_cast<uint8_t*>(c->d_slab[slot]);
+        uint8_t* slab = reinterpret_cast<uint8_t*>(c->d_slab[slot].get());
         uint8_t* mine = slab + (size_t)c->rank * slice;  // in-place send slot
         if (c->slab_stream[slot] && c->slab_stream[slot] != st)
             HIPCHK(c, hipStreamWaitEvent(st, c->ev_gath[slot], 0));
         hs.lap(2);
         if ((r = launch(c, s, &pp, rows, reinterpret_cast<uint32_t*>(mine), nullptr, st, kflags, 0u, 0, &bm)) != RRTE_OK)
             return r;
-        if (c->comm_size == 1 && c->emu_peers > 1 && c->rank == root) {  // RRTE_EMULATE_PEERS (tests)
+        if (c->comm_size == 1 && c->env.emu_peers > 1 && c->rank == root) {  // RRTE_EMULATE_PEERS (tests)
             const LaunchPlan L = plan_launch(c, s, &pp, rows, kflags, 0u, &bm);
             if ((r = render_peers(c, L, L.k.cam, 1, slab, slice, 0, root, st)) != RRTE_OK) return r;
         }
@@ -657,17 +657,17 @@ rrte_status rrte_hip_comm_init(rrte_ctx* c, int nranks, int rank, const uint8_t 
     c->nranks = nranks;
     c->rank = rank;
     c->comm_size = nranks;
-    if (nranks == 1 && c->emu_peers > 1) {
+    if (nranks == 1 && c->env.emu_peers > 1) {
         // RRTE_EMULATE_PEERS=N: the root of N ranks whose peers' shares it renders itself (render_peers)
-        c->nranks = c->emu_peers;
+        c->nranks = c->env.emu_peers;
         c->rank = 0;
-    } else if (nranks == 1 && c->emu_nranks > 1) {
+    } else if (nranks == 1 && c->env.emu_nranks > 1) {
         // RRTE_EMULATE_RANK=N:R with a 1-rank communicator (diagnostic, one GPU): the gather path lays
         // frames out as rank R of N -- R's bands rendered into its slab slice, the 1-rank gather moving
         // that slice, and on rank 0 the de-interleave of all N slices (the other N-1 hold whatever the
         // receive buffer held) -- i.e. one rank's whole per-frame cost except the xGMI transfers.
-        c->nranks = c->emu_nranks;
-        c->rank = c->emu_rank;
+        c->nranks = c->env.emu_nranks;
+        c->rank = c->env.emu_rank;
     }
     return RRTE_OK;
 }
@@ -711,7 +711,7 @@ rrte_status rrte_hip_render_gather(rrte_ctx* c, const rrte_scene_ir* s, const rr
     const size_t npix = (size_t)p->width * p->height;
     uint32_t* full = nullptr;
     if (c->rank == root) {
-        if ((r = ensure(c, c->d_full, c->cap_full, npix)) != RRTE_OK) return r;
+        if ((r = ensure(c, c->d_full, npix)) != RRTE_OK) return r;
         full = c->d_full;
     }
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));

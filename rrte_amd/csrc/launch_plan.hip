@@ -55,7 +55,7 @@ KParams make_params(const rrte_ctx* c, const rrte_scene_ir* s, const rrte_render
     float m[16];
     mat4_srt(trs, m);
     to_affine12(m, fc.cam_xf);
-    k.debug = c->env_debug;  // RRTE_DEBUG ablation bits (profiling only)
+    k.debug = c->env.debug;  // RRTE_DEBUG ablation bits (profiling only)
     return k;
 }
 
@@ -100,7 +100,7 @@ static void fill_tile_rects(rrte_ctx* c, const rrte_scene_ir* s, const rrte_rend
 static void tile_rects(bool enabled, const std::vector<float4>& bounds, const rrte_scene_ir* s, const rrte_render_params* p,
                        KParams& kk);
 static void fill_tile_rects_uncached(const rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_params* p, KParams& kk) {
-    tile_rects(c->env_tile_cull, c->h_bounds, s, p, kk);
+    tile_rects(c->env.tile_cull, c->h_bounds, s, p, kk);
 }
 static void tile_rects(bool enabled, const std::vector<float4>& bounds, const rrte_scene_ir* s, const rrte_render_params* p,
                        KParams& kk) {
@@ -382,7 +382,7 @@ LaunchPlan plan_launch(rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_pa
     L.k.row0 = row0;  // (image rows [row0, row0 + rows); band_rows == 0)
     L.k.flags |= internal_flags;
     L.mode = (int)p->mode;
-    L.cull = cull_policy(s, p->mode, c->env_cull);
+    L.cull = cull_policy(s, p->mode, c->env.cull);
     // single-sample, single-bounce frames get the straight-line specialisation (SINGLE); others the
     // specialisation with runtime sample / bounce loops
     L.single = p->samples_per_pixel == 1 && (p->mode == RRTE_MODE_LAMBERT_SHADOW || p->max_depth <= 1);
@@ -407,7 +407,7 @@ const BandMap& frame_band_map(rrte_ctx* c, const rrte_scene_ir* s, const rrte_re
           bc.nranks == c->nranks && bc.root == root && bc.rank == c->rank &&
           !memcmp(&bc.cam, &s->camera, sizeof bc.cam))) {
         bc.m = band_layout(s->camera, c->h_bounds, s->num_prims, p->width, p->height, p->band_rows, c->nranks, root,
-                           c->env_band_sky);
+                           c->env.band_sky);
         bc.valid = true;
         bc.gen = c->scene_gen;
         bc.w = p->width;

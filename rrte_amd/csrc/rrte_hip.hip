@@ -3,27 +3,30 @@
 // (Melthizar/RRTE crates/rrte-renderer/src/raytracer.rs:45-148).
 //
 // This file is the launch itself and the only one that instantiates the ray and query kernels
-// (ray_kernel, ray_kernel_accel, ray_query_kernel, ray_query_accel_kernel): kernel selection, the
+// (ray_kernel, ray_kernel_accel, ray_query_kernel, ray_query_accel_kernel): the
 // launch, the counters, the blocking frame paths, the render entry points and the ray queries.
 // The rest of the host side lives beside it, around one private header (context.hpp: rrte_ctx and
 // what the units share).  No exception crosses the ABI.
 //
 // Where a function lives (headers and documents that say "rrte_hip.hip X" mean the unit below):
 //   context.hip       rrte_hip_create / destroy / synchronize / stats / check_word, the environment
-//                     switches, the setters and info getters, host_register / unregister,
-//                     retire / retired_done / wait_retired
+//                     switches (read_env), the setters and info getters, host_register / unregister,
+//                     retire / retired_done / wait_retired (context.hpp: struct Version over them;
+//                     resources.hpp: the owning buffer, event and stream types)
 //   scene_upload.hip  validate, validate_scene, lower_scene, prim_bound, the mat4 restatement,
 //                     scene_key_parts, the mesh cache, topology_of, scene_features,
 //                     scene_records_check, upload_scene, rrte_hip_mesh_refit / mesh_nodes / mesh_slots,
 //                     rrte_hip_sdf_guards
 //   launch_plan.hip   make_params, tile_rects / fill_tile_rects, rows_for_rank, sky_band_count,
 //                     band_layout, cull_policy, plan_launch, frame_band_map and their context-free exports
-//   rrte_hip.hip      jit_kernel_for / jit_lookup (jit_pending), the tile order of a launch (TileProfile:
-//                     lpt_slots, upload_hot_list, plan_tile_order: issue_launch is its only caller),
-//                     launch_generic (the generic kernel variant), plain_launch, issue_launch, launch,
+//   jit_select.hip    jit_kernel_for / jit_lookup (jit_pending), jit_wants_topology, jit_key,
+//                     jit_uniform_guards, rrte_hip_jit_check / build_id / jit_cache_key
+//   tile_order.hip    the tile order of a launch (TileProfile: lpt_slots, fixed_slots, reserve_hot_lists,
+//                     upload_hot_list, plan_tile_order, finish_tile_order: issue_launch is their only
+//                     caller), rrte_hip_tile_order_plan
+//   rrte_hip.hip      launch_generic (the generic kernel variant), plain_launch, issue_launch, launch,
 //                     resolve_counters, finish_frame,
-//                     render_chunked, render_common, dump_if_asked, rrte_hip_render*, the ray queries,
-//                     rrte_hip_jit_check / build_id / jit_cache_key
+//                     render_chunked, render_common, dump_if_asked, rrte_hip_render*, the ray queries
 //   gather.hip        rrte_hip_comm_*, slab_rgb24, deinterleave, render_peers, render_batch,
 //                     flush_batch, gather_frame, nccl_settle, comm_abort, poll_events, wait_bounded,
 //                     rrte_hip_render_gather* / flush / set_gather_batch / gather_info
@@ -35,362 +38,13 @@
 #include <cstdlib>
 #include <cstddef>
 #include <cstring>
-#include <future>
 
 #include "context.hpp"
-#include "sdf_guard.hpp"
 #include "ray_query.hpp"
 
 using namespace rrte;
 
 namespace rrte {
-
-// Scene-specialised kernel for the cached scene + mode, compiling it if the
-// JIT policy says so; nullptr = use the generic kernel.
-constexpr uint32_t kJitMaxPrims = 128, kJitMaxNodes = 1024;
-
-// FULL or TOPOLOGY kernel (RRTE_JIT_TOPO, rrte_hip.h).  Adaptive: topology while the scene's values keep
-// changing under one topology (one compile for a whole animation), full once the scene has been
-// rendered unchanged for kJitFullAfter frames (until that full kernel is ready, the topology kernel).
-constexpr uint64_t kJitFullAfter = 16;
-
-static bool jit_wants_topology(const rrte_ctx* c) {
-    return c->env_jit_topo == 1 ||
-           (c->env_jit_topo == 2 && c->value_edits >= 1 && c->same_scene_renders < kJitFullAfter);
-}
-
-static std::string jit_key(const rrte_ctx* c, bool topo, int mode, bool cull, bool single, bool uniform) {
-    std::string key(1, topo ? 'T' : 'F');
-    if (topo) key += c->topo_key;
-    else key.append(c->scene_key.begin(), c->scene_key.end());
-    key.push_back((char)mode);
-    key.push_back((char)cull);
-    key.push_back((char)single);
-    key.push_back((char)uniform);
-    return key;
-}
-
-static bool jit_uniform_guards(const rrte_ctx* c) { return c->env_guard_policy == 2 ? c->jit_stream : c->env_guard_policy == 1; }
-
-// The cached kernel for `key`, compiling it if the JIT policy says so; nullptr = not available (yet).
-static JitKernel* jit_lookup(rrte_ctx* c, const std::string& key, bool topo, int mode, bool cull, bool single, bool uniform) {
-    auto it = c->jit_cache.find(key);
-    if (it != c->jit_cache.end()) return it->second.fn ? &it->second : nullptr;
-    JitKernel jk;
-    std::string log;
-    auto pend = c->jit_pending.find(key);
-    if (pend != c->jit_pending.end()) {
-        // AUTO: a background compile of this kernel is running; keep the current kernel until it lands
-        if (pend->second.wait_for(std::chrono::seconds(0)) != std::future_status::ready) return nullptr;
-        const JitCode jc = pend->second.get();
-        c->jit_pending.erase(pend);
-        trace_rec(c, "jit: module load begin", nullptr, nullptr, (uint32_t)jc.code.size());
-        const bool loaded = hipSetDevice(c->device) == hipSuccess && jit_load(jc, jk, log);
-        trace_rec(c, "jit: module load end", nullptr, nullptr, loaded);
-        if (!loaded) {
-            c->jit_log = log;
-            jk = JitKernel{};
-        } else {
-            c->stats.jit_compile_ms = jk.compile_ms;
-        }
-    } else {
-        if (!(c->jit_mode == RRTE_JIT_ON || c->same_scene_renders >= 1 || topo)) return nullptr;
-        if (c->jit_cache.size() >= 32) {
-            // frames launched from these modules may still run on caller streams (a mode / cull /
-            // sample-count change does not re-upload the scene, so upload_scene's sync has not run)
-            // (bounded: RRTE_RCCL_ERROR surfaces at the next gather call if a stalled gather blocks it)
-            if (hipSetDevice(c->device) != hipSuccess || retire(c, c->launched) != RRTE_OK ||
-                wait_retired(c, c->launched) != RRTE_OK)
-                return nullptr;
-            for (auto& kv : c->jit_cache) jit_release(kv.second);
-            c->jit_cache.clear();
-            c->jit_last.valid = false;
-        }
-        std::string src = jit_source(c->h_prims.data(), (uint32_t)c->h_prims.size(), c->h_mats.data(),
-                                     (uint32_t)c->h_mats.size(), c->h_lights.data(), (uint32_t)c->h_lights.size(),
-                                     c->h_nodes.data(), (uint32_t)c->h_nodes.size(), mode, cull, single,
-                                     topo ? &c->topo : nullptr);
-        if (uniform) src = "#define RRTE_GUARD_UNIFORM 1\n" + src;
-        if (c->jit_mode == RRTE_JIT_AUTO) {
-            // compile on a background thread (hiprtc only); frames keep running on the current kernel
-            c->jit_pending.emplace(key, std::async(std::launch::async, [src]() { return jit_compile_code(src); }));
-            return nullptr;
-        }
-        if (hipSetDevice(c->device) != hipSuccess || !jit_compile(src, jk, log)) {
-            c->jit_log = log;  // stay on the generic kernel for this scene
-            jk = JitKernel{};
-        } else {
-            c->stats.jit_compile_ms = jk.compile_ms;
-        }
-    }
-    jk.topology = topo;
-    auto& slot = c->jit_cache[key];
-    slot = jk;
-    return slot.fn ? &slot : nullptr;
-}
-
-static JitKernel* jit_kernel_for(rrte_ctx* c, int mode, bool cull, bool single) {
-    if (c->jit_mode == RRTE_JIT_OFF) return nullptr;
-    auto& last = c->jit_last;  // per-frame fast path: same scene, mode, policy and kernel kind as the last frame
-    const bool topo = jit_wants_topology(c);
-    const bool uniform = jit_uniform_guards(c);
-    if (last.valid && last.gen == c->scene_gen && last.mode == mode && last.cull == cull && last.single == single &&
-        last.jit_mode == c->jit_mode && last.topo == topo && last.uniform == uniform)
-        return last.k;
-    if (c->h_prims.size() > kJitMaxPrims || c->h_nodes.size() > kJitMaxNodes) return nullptr;
-    const std::string key = jit_key(c, topo, mode, cull, single, uniform);
-    JitKernel* k = jit_lookup(c, key, topo, mode, cull, single, uniform);
-    if (!k && !c->jit_cache.count(key)) {
-        // not available yet (AUTO: not due, or compiling in the background): not remembered, asked again
-        // next frame.  The full kernel of a scene that stopped changing: its topology kernel meanwhile
-        if (!topo && c->env_jit_topo == 2 && c->value_edits >= 1) {
-            auto it = c->jit_cache.find(jit_key(c, true, mode, cull, single, uniform));
-            if (it != c->jit_cache.end() && it->second.fn) return &it->second;
-        }
-        return nullptr;
-    }
-    last.gen = c->scene_gen;
-    last.mode = mode;
-    last.jit_mode = c->jit_mode;
-    last.cull = cull;
-    last.single = single;
-    last.topo = topo;
-    last.uniform = uniform;
-    last.k = k;
-    last.valid = true;
-    return k;
-}
-
-// Measured-cost tile order (rrte_ctx::TileProfile, KParams::hot).
-constexpr uint64_t kTileReprofile = 256;  // launches of one shape between two profiles (each costs a list upload)
-constexpr uint64_t kTileReprofileMoving = 32;  // ... when the camera has moved since the last profile
-
-static uint64_t fnv1a(const void* p, size_t n) {
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) h = (h ^ static_cast<const unsigned char*>(p)[i]) * 1099511628211ull;
-    return h;
-}
-
-// Every tile of a profile (costs[0 .. n), tiles_x per row), slowest first (longest-processing-time
-// order), as packed slots: a counting sort on 65536 cost buckets (ties in tile order), O(tiles) on the
-// host.
-static std::vector<uint32_t> lpt_slots(const uint32_t* costs, uint32_t n, uint32_t tiles_x) {
-    std::vector<uint32_t> slots;
-    if (n == 0 || tiles_x == 0) return slots;
-    uint32_t mx = 0;
-    for (uint32_t i = 0; i < n; ++i) mx = std::max(mx, costs[i]);
-    constexpr uint32_t B = 65536;
-    std::vector<uint32_t> cnt(B + 1, 0u);
-    auto bucket = [&](uint32_t c) { return B - 1 - (mx ? (uint32_t)((uint64_t)c * (B - 1) / mx) : 0u); };
-    for (uint32_t i = 0; i < n; ++i) ++cnt[bucket(costs[i])];
-    uint32_t acc = 0;
-    for (uint32_t b = 0; b <= B; ++b) {
-        const uint32_t c = cnt[b];
-        cnt[b] = acc;
-        acc += c;
-    }
-    slots.resize(n);
-    for (uint32_t i = 0; i < n; ++i) slots[cnt[bucket(costs[i])]++] = hot_pack(i % tiles_x, i / tiles_x);
-    return slots;
-}
-
-// RRTE_TILE_ORDER=2 (tests): every tile once in a fixed scrambled order -- slot k takes tile
-// (k * stride) mod n for a stride near 0.618 n coprime with n -- so the list path runs on every launch
-// without a profile.
-static std::vector<uint32_t> fixed_slots(uint32_t n, uint32_t tiles_x) {
-    std::vector<uint32_t> slots(n);
-    uint64_t stride = std::max<uint64_t>(1, (uint64_t)(0.618034 * n));
-    auto gcd = [](uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; };
-    while (n > 1 && gcd(stride, n) != 1) ++stride;
-    for (uint32_t k = 0; k < n; ++k) {
-        const uint32_t i = (uint32_t)((k * stride) % n);
-        slots[k] = hot_pack(i % tiles_x, i / tiles_x);
-    }
-    return slots;
-}
-
-// Words per XCD of a tile list of n slots stored XCD-major (KParams::hot_stride).
-static uint32_t hot_stride(uint32_t n) { return (n + 7u) / 8u; }
-
-// Allocates what an upload of up to `words` list words needs -- the pinned staging arena and the device
-// versions not yet allocated -- at profile time, so the first upload (inside a later render call)
-// allocates nothing.  The copies run on the context's upload stream, created with the context: a
-// stream's first use sets up its hardware queue (~8 ms measured, profiles/r06_engine_loop_trace.log),
-// which must not land in a frame.  false = not now (a copy out of the arena is still pending).
-static bool reserve_hot_lists(rrte_ctx::TileProfile& tp, size_t words) {
-    constexpr int K = rrte_ctx::TileProfile::kVersions;
-    if (tp.arena_words < words) {
-        for (int i = 0; i < K; ++i)
-            if (tp.ev_up[i] && hipEventQuery(tp.ev_up[i]) != hipSuccess) return false;
-        if (tp.h_arena) (void)hipHostFree(tp.h_arena);
-        tp.h_arena = nullptr;
-        tp.arena_words = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&tp.h_arena), K * words * sizeof(uint32_t), hipHostMallocDefault) !=
-            hipSuccess)
-            return false;
-        tp.arena_words = words;
-    }
-    for (int i = 0; i < rrte_ctx::TileProfile::kVersions; ++i)
-        if (!tp.d_list[i]) {
-            if (hipMalloc(reinterpret_cast<void**>(&tp.d_list[i]), words * sizeof(uint32_t)) != hipSuccess) return false;
-            tp.cap_list[i] = words;
-        }
-    return true;
-}
-
-// Uploads the composed slots into a free version of the device list; false leaves the launch on the
-// current list (or in image order) -- it never waits for the device.  The current version is retired
-// first; a version is free once every launch that read it has completed (struct Retire).  The copy
-// runs on the list's own upload stream; its event orders every stream's first launch that reads the
-// version after it (plan_tile_order), so every launch sees a whole list and no render call waits.
-static bool upload_hot_list(rrte_ctx* c, rrte_ctx::TileProfile& tp) {
-    constexpr int K = rrte_ctx::TileProfile::kVersions;
-    int pick = -1;
-    for (int k = 1; k <= K && pick < 0; ++k) {  // the oldest retired version first
-        const int v = (int)((tp.uploads + (uint64_t)k) % K);
-        if (v != tp.cur && retired_done(tp.ret[v])) pick = v;
-    }
-    if (pick < 0) return false;
-    trace_rec(c, "hot-list upload: begin", nullptr, nullptr, (uint32_t)pick);
-    tp.ret[pick].nev = 0;
-    const size_t n = tp.slots.size(), stride = hot_stride((uint32_t)n);
-    const size_t words = 8u * stride;  // XCD-major (KParams::hot_stride)
-    const size_t bytes = words * sizeof(uint32_t);
-    if (tp.cap_list[pick] < words) {  // a larger frame: its launches have completed, the old buffer is idle
-        if (tp.d_list[pick]) c->graveyard.push_back(tp.d_list[pick]);
-        tp.d_list[pick] = nullptr;
-        tp.cap_list[pick] = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&tp.d_list[pick]), bytes) != hipSuccess) return false;
-        tp.cap_list[pick] = words;
-    }
-    trace_rec(c, "hot-list upload: device buffer", nullptr, nullptr, (uint32_t)pick);
-    if (!reserve_hot_lists(tp, words)) return false;
-    trace_rec(c, "hot-list upload: reserved", nullptr, nullptr, (uint32_t)pick);
-    uint32_t* stage = tp.h_arena + (size_t)pick * tp.arena_words;
-    for (size_t k = 0; k < n; ++k) stage[(k & 7u) * stride + (k >> 3)] = tp.slots[k];
-    // fault injection for the device index check (tests): only where the check stops the wave first
-    if (c->env_fault_bad_slot == 1 && (c->env_debug & 4u) && n) stage[0] = hot_pack(0u, 0xfff0u);
-    if (!tp.ev_up[pick] && hipEventCreateWithFlags(&tp.ev_up[pick], hipEventDisableTiming) != hipSuccess) return false;
-    trace_rec(c, "hot-list upload: staged", nullptr, nullptr, (uint32_t)pick);
-    if (hipMemcpyAsync(tp.d_list[pick], stage, bytes, hipMemcpyHostToDevice, c->upload_stream) != hipSuccess)
-        return false;
-    trace_rec(c, "hot-list upload: copy queued", c->upload_stream, nullptr, (uint32_t)bytes);
-    if (hipEventRecord(tp.ev_up[pick], c->upload_stream) != hipSuccess) return false;
-    tp.ordered[pick].clear();
-    if (tp.cur >= 0 && retire(c, tp.ret[tp.cur]) != RRTE_OK) return false;
-    tp.cur = pick;
-    ++tp.uploads;
-    return true;
-}
-
-// Sets the plan's tile order (slot list, tile profile) for a launch of kernel `kern`; true when this
-// launch is profiled (the caller copies the durations back after it).
-static bool plan_tile_order(rrte_ctx* c, LaunchPlan& L, const void* kern, hipStream_t st) {
-    KParams& k = L.k;
-    k.tiles_x = L.gx;
-    k.hot = nullptr;
-    k.hot_n = 0;
-    k.hot_stride = 0;
-    k.tile_cost = nullptr;
-    // (RRTE_DEBUG bit 5 runs one workgroup in image-order numbering: no tile order; bit 4's per-wave
-    // stamps work with it)
-    if (!c->env_tile_order || L.gx > 0xffffu || L.gy > 0xffffu || (k.debug & 32u)) return false;
-    auto& tp = c->tprof[L.prof];
-    std::string key(reinterpret_cast<const char*>(&kern), sizeof kern);
-    const uint32_t shape[] = {k.width, k.height, k.rows, k.row0, k.band_rows, k.nranks, k.rank, k.spp, k.max_depth,
-                              (uint32_t)L.mode, (uint32_t)L.cull, (uint32_t)L.single, k.tile_shift};
-    key.append(reinterpret_cast<const char*>(shape), sizeof shape);
-    const uint32_t tiles = L.gx * L.gy;
-    if (tp.pending && hipEventQuery(tp.ev) == hipSuccess) {
-        trace_rec(c, "tile plan: profile landed", st, nullptr);
-        tp.pending = false;
-        if (tp.pending_key == key) {
-            // the order is composed on a worker thread from a copy of the durations: a whole frame's
-            // counting sort takes ~0.5 ms of host time that a render call must not stall for
-            std::vector<uint32_t> costs(tp.h_cost, tp.h_cost + tp.tiles);
-            const uint32_t tx = tp.tiles_x;
-            tp.work = std::async(std::launch::async, [key, costs = std::move(costs), tx]() {
-                return TilePlanResult{key, lpt_slots(costs.data(), (uint32_t)costs.size(), tx)};
-            });
-            tp.working = true;
-            tp.launches = 0;
-            ++tp.profiles;
-        }
-    }
-    if (tp.working && tp.work.wait_for(std::chrono::seconds(0)) == std::future_status::ready) {
-        trace_rec(c, "tile plan: worker result", st, nullptr);
-        TilePlanResult r = tp.work.get();
-        tp.working = false;
-        if (r.key == key && r.slots.size() == tiles) {  // (a result for another shape is dropped)
-            tp.key = key;
-            tp.slots = std::move(r.slots);
-            tp.fixed = false;
-            if (tp.cur >= 0 && retire(c, tp.ret[tp.cur]) != RRTE_OK) return false;
-            tp.cur = -1;
-        }
-    }
-    if (tp.key != key) {  // another shape: drop the list, profile as soon as the copy buffer is free
-        tp.key = key;
-        tp.slots.clear();
-        tp.fixed = c->env_tile_order_fixed;
-        if (tp.fixed) tp.slots = fixed_slots(tiles, L.gx);
-        if (tp.cur >= 0 && retire(c, tp.ret[tp.cur]) != RRTE_OK) return false;
-        tp.cur = -1;
-        tp.launches = kTileReprofile;
-    }
-    if (tp.fixed) tp.launches = 0;  // RRTE_TILE_ORDER=2: the fixed list, never profiled
-    // a moving camera moves the expensive tiles: re-profile after kTileReprofileMoving launches instead
-    const uint64_t cam = fnv1a(&k.cam[0], offsetof(FrameCam, tile_cull));
-    const bool moved = cam != tp.cam_sig;
-    const uint64_t every = c->env_test_recycle ? 1 : kTileReprofile, moving = c->env_test_recycle ? 1 : kTileReprofileMoving;
-    const bool profile = !tp.pending && (tp.launches >= every || (moved && tp.launches >= moving));
-    ++tp.launches;
-    // RRTE_TEST_RECYCLE=1: a new list version every launch (the fixed list re-uploaded), so the
-    // version pool wraps within kVersions launches
-    // (into a free version, retiring the current one; with none free the launch keeps the current list)
-    if (c->env_test_recycle && tp.fixed && tp.cur >= 0) (void)upload_hot_list(c, tp);
-    if (!tp.slots.empty() && tp.slots.size() == tiles && (tp.cur >= 0 || upload_hot_list(c, tp))) {
-        auto& ord = tp.ordered[tp.cur];  // (first launch of this stream on the version: after its upload)
-        if (tp.ev_up[tp.cur] && std::find(ord.begin(), ord.end(), st) == ord.end()) {
-            if (ev_wait(c, st, tp.ev_up[tp.cur], "wait tile-list upload") != hipSuccess) return false;
-            ord.push_back(st);
-        }
-        k.hot = tp.d_list[tp.cur];
-        k.hot_n = (uint32_t)tp.slots.size();
-        k.hot_stride = hot_stride(k.hot_n);
-        tp.ret[tp.cur].use(st);
-    }
-    if (!profile) return false;
-    if (ensure(c, tp.d_cost, tp.cap_d, tiles) != RRTE_OK) return false;
-    if (tp.cap_h < tiles) {
-        if (tp.h_cost) (void)hipHostFree(tp.h_cost);  // (no copy into it is pending: !tp.pending)
-        tp.h_cost = nullptr;
-        tp.cap_h = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&tp.h_cost), tiles * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-            return false;
-        tp.cap_h = tiles;
-    }
-    if (!tp.ev && hipEventCreateWithFlags(&tp.ev, hipEventDisableTiming) != hipSuccess) return false;
-    trace_rec(c, "tile profile: reserve lists", st, nullptr, tiles);
-    if (!reserve_hot_lists(tp, 8u * (size_t)hot_stride(tiles))) return false;
-    trace_rec(c, "tile profile: reserved", st, nullptr, tiles);
-    k.tile_cost = tp.d_cost;  // every tile of frame 0 stores its duration (no clearing needed)
-    tp.cam_sig = cam;
-    tp.pending_key = key;
-    tp.tiles = tiles;
-    tp.tiles_x = L.gx;
-    return true;
-}
-
-// Queues the profiled launch's copy-back on its stream (plan_tile_order returned true).
-static rrte_status finish_tile_order(rrte_ctx* c, const LaunchPlan& L, bool profile, hipStream_t st) {
-    auto& tp = c->tprof[L.prof];
-    if (!profile) return RRTE_OK;
-    HIPCHK(c, hipMemcpyAsync(tp.h_cost, tp.d_cost, (size_t)tp.tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, ev_record(c, tp.ev, st, "record tile-profile copy"));
-    tp.pending = true;
-    return RRTE_OK;
-}
 
 // The generic kernel variant for a scene with features `need` (kFeat*): the first of the
 // precompiled feature sets F0, F1, F2 that covers it, else every feature (scene_view.hpp SceneView).
@@ -419,7 +73,7 @@ static void launch_generic(uint32_t need, dim3 grid, dim3 block, hipStream_t st,
 static bool plain_launch(const rrte_ctx* c, const JitKernel* jk, const LaunchPlan& L, const uint32_t* d_rgba,
                          const float4* d_f32) {
     const KParams& k = L.k;
-    return c->env_jit_plain && jk->fn_plain && L.single && d_rgba && !d_f32 && !c->host_out &&
+    return c->env.jit_plain && jk->fn_plain && L.single && d_rgba && !d_f32 && !c->host_out &&
            k.nframes == 1 && k.band_rows == 0 && k.row0 == 0 && k.out_image_rows == 0 && k.debug == 0 &&
            !(k.flags & (kFlagSlabRgb24 | kFlagHostStore)) && k.inv_gamma == kInvGamma22 && k.inv_spp == 1.0f;
 }
@@ -432,7 +86,7 @@ static rrte_status accel_launch_view(rrte_ctx* c, hipStream_t st, AccelView& av,
     av = c->accel;
     if (!(c->accel_flags & RRTE_ACCEL_COUNT)) return RRTE_OK;
     av.count = c->d_counters + 2;
-    if (!c->ev_accel) HIPCHK(c, hipEventCreateWithFlags(&c->ev_accel, hipEventDisableTiming));
+    HIPCHK(c, c->ev_accel.create());
     if (fresh) HIPCHK(c, hipMemsetAsync(c->d_counters + 2, 0, 2 * sizeof(unsigned long long), st));
     return RRTE_OK;
 }
@@ -457,20 +111,10 @@ rrte_status issue_launch(rrte_ctx* c, LaunchPlan& L, uint32_t* d_rgba, float4* d
     // 64-thread workgroups: (tile column, frame, tile row or slot row), KParams::hot
     const bool profile = plan_tile_order(c, L, jk ? (const void*)jk->fn : nullptr, st);
     c->stats.hot_tiles = L.k.hot_n;
-    if (c->sb_cur >= 0) {  // the launch reads the current scene version: after its upload, tracked until retired
-        rrte_ctx::SceneBuf& B = c->sb[c->sb_cur];
-        if (std::find(B.ordered.begin(), B.ordered.end(), st) == B.ordered.end()) {
-            HIPCHK(c, ev_wait(c, st, B.ev_up, "wait scene upload"));
-            B.ordered.push_back(st);
-        }
-        B.ret.use(st);
-    }
+    // the launch reads the current scene version: after its upload, tracked until retired
+    if (c->sb_cur >= 0) HIPCHK(c, c->sb[c->sb_cur].ver.begin_read(c, st, "wait scene upload"));
     c->launched.use(st);
-    if (c->ctr_pending && st != c->stream &&
-        std::find(c->ctr_ordered.begin(), c->ctr_ordered.end(), st) == c->ctr_ordered.end()) {
-        HIPCHK(c, ev_wait(c, st, c->ev_ctr[c->ctr_slot], "wait counter snapshot"));
-        c->ctr_ordered.push_back(st);
-    }
+    if (c->ctr_pending && st != c->stream) HIPCHK(c, c->ctr[c->ctr_slot].wait_upload(c, st, "wait counter snapshot"));
     const dim3 grid(L.gx, L.k.nframes, L.gy), block(kBlockThreads);
     trace_rec(c, profile ? "launch ray (profiled)" : "launch ray", st, nullptr, L.k.nframes, L.k.rows);
     if (jk) {
@@ -507,7 +151,7 @@ rrte_status issue_launch(rrte_ctx* c, LaunchPlan& L, uint32_t* d_rgba, float4* d
         if ((ar = accel_launch_done(c, st)) != RRTE_OK) return ar;
         return finish_tile_order(c, L, profile, st);
     }
-    const uint32_t need = c->env_generic_all ? (kFeatAll | (c->scene_feat & kFeatInstance)) : c->scene_feat;
+    const uint32_t need = c->env.generic_all ? (kFeatAll | (c->scene_feat & kFeatInstance)) : c->scene_feat;
     if (L.mode == RRTE_MODE_REFCOMPAT)
         launch_generic<RRTE_MODE_REFCOMPAT, false, 0u, kFeatAnalytic, kFeatSdf>(need, grid, block, st, k, sv, cl, d_rgba,
                                                                              d_f32, c->d_counters);
@@ -550,7 +194,7 @@ static unsigned long long ctr_total(rrte_ctx* c, int slot) {
 // The last blocking frame's shadow-ray count into rrte_stats (waits for its counter copy).
 rrte_status resolve_counters(rrte_ctx* c) {
     if (!c->ctr_pending) return RRTE_OK;
-    HIPCHK(c, hipEventSynchronize(c->ev_ctr[c->ctr_slot]));
+    HIPCHK(c, hipEventSynchronize(c->ctr[c->ctr_slot].ev_up));
     const unsigned long long total = ctr_total(c, c->ctr_slot);
     c->stats.shadow_rays = total - c->shadow_base;
     c->shadow_base = total;
@@ -581,7 +225,7 @@ rrte_status finish_frame(rrte_ctx* c, bool deferred) {
     const int slot = c->ctr_pending ? 1 - c->ctr_slot : 0;
     if (deferred) HIPCHK(c, hipEventRecord(c->ev_done, c->stream));
     HIPCHK(c, hipMemcpyAsync(ctr_host(c, slot), c->d_counters, kCounterBytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_ctr[slot], c->stream));
+    HIPCHK(c, c->ctr[slot].published(c->stream));  // (no stream has waited for this snapshot yet)
     rrte_status r = deferred ? spin_wait(c, c->ev_done) : RRTE_OK;
     if (r != RRTE_OK) return r;
     trace_rec(c, "frame complete (host)", c->stream, nullptr);
@@ -594,7 +238,6 @@ rrte_status finish_frame(rrte_ctx* c, bool deferred) {
     }
     c->ctr_slot = slot;
     c->ctr_pending = true;
-    c->ctr_ordered.clear();
     if (!deferred && (r = resolve_counters(c)) != RRTE_OK) return r;
     if (c->pending_kernel_timing) {
         float ms = 0.0f;
@@ -618,11 +261,11 @@ static rrte_status render_chunked(rrte_ctx* c, const rrte_scene_ir* s, const rrt
     const uint32_t rows = (((H + n - 1) / n) + 15u) & ~15u;
     n = (H + rows - 1) / rows;
     for (uint32_t i = 0; i < n; ++i) {
-        if (!c->bnd_stream[i]) HIPCHK(c, hipStreamCreateWithFlags(&c->bnd_stream[i], hipStreamNonBlocking));
-        if (!c->ev_bchunk[i]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bchunk[i], hipEventDisableTiming));
+        HIPCHK(c, c->bnd_stream[i].create());
+        HIPCHK(c, c->ev_bchunk[i].create());
     }
-    if (!c->bnd_copy) HIPCHK(c, hipStreamCreateWithFlags(&c->bnd_copy, hipStreamNonBlocking));
-    if (!c->ev_bcopy) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bcopy, hipEventDisableTiming));
+    HIPCHK(c, c->bnd_copy.create());
+    HIPCHK(c, c->ev_bcopy.create());
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));  // after the work already queued on the context's stream
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t r0 = i * rows, nr = std::min(rows, H - r0);
@@ -668,7 +311,7 @@ static uint32_t* pinned_device_ptr(void* host, size_t bytes) {
 // RRTE_DUMP_SCENE (diagnostics): the frame's scene and parameters, as given, into the dump file
 // before anything else happens to them (rrte_hip_scene_dump; replayable on the oracle or the device).
 void dump_if_asked(const rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_params* p) {
-    if (!c->dump_path.empty() && s && p) (void)rrte_hip_scene_dump(s, p, c->dump_path.c_str());
+    if (!c->env.dump_path.empty() && s && p) (void)rrte_hip_scene_dump(s, p, c->env.dump_path.c_str());
 }
 
 static rrte_status render_common(rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_params* p, uint8_t* out8,
@@ -680,24 +323,24 @@ static rrte_status render_common(rrte_ctx* c, const rrte_scene_ir* s, const rrte
     double up = 0.0;
     if ((r = upload_scene(c, s, c->stream, &up)) != RRTE_OK) return r;
     const size_t npix = (size_t)p->width * p->height;
-    if ((r = ensure(c, c->d_rgba, c->cap_rgba, npix)) != RRTE_OK) return r;
-    if (outf && (r = ensure(c, c->d_f32, c->cap_f32, npix)) != RRTE_OK) return r;
+    if ((r = ensure(c, c->d_rgba, npix)) != RRTE_OK) return r;
+    if (outf && (r = ensure(c, c->d_f32, npix)) != RRTE_OK) return r;
     // single-context render: all rows, no band mapping
     const int nr = c->nranks, rk = c->rank;
     c->nranks = 1;
     c->rank = 0;
     c->jit_stream = false;  // (one blocking frame: the latency flavour of the specialised kernel)
     // pinned caller buffer: the kernel writes the frame into it directly (no D2H copy afterwards)
-    uint32_t* zc = out8 && !outf && c->env_bnd_zerocopy ? pinned_device_ptr(out8, npix * 4) : nullptr;
-    const bool chunked = !zc && out8 && !outf && c->bnd_chunks > 1 && p->height >= 32u && !(c->env_debug & ~4u);  // (bit 2, the index check, keeps every path)
+    uint32_t* zc = out8 && !outf && c->env.bnd_zerocopy ? pinned_device_ptr(out8, npix * 4) : nullptr;
+    const bool chunked = !zc && out8 && !outf && c->env.bnd_chunks > 1 && p->height >= 32u && !(c->env.debug & ~4u);  // (bit 2, the index check, keeps every path)
     if (chunked) {
-        r = render_chunked(c, s, p, out8, (uint32_t)c->bnd_chunks);
+        r = render_chunked(c, s, p, out8, (uint32_t)c->env.bnd_chunks);
     } else {
         HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-        if (zc) c->tile_shift = c->zc_tile_shift;  // whole 128-B lines per wave across PCIe
+        if (zc) c->tile_shift = c->env.zc_tile_shift;  // whole 128-B lines per wave across PCIe
         c->host_out = zc != nullptr;
         r = launch(c, s, p, p->height, zc ? zc : c->d_rgba, outf ? c->d_f32 : nullptr, c->stream,
-                   zc && c->env_zc_system_store ? kFlagHostStore : 0u, 0u, zc ? rrte_ctx::kZcProf : 0);
+                   zc && c->env.zc_system_store ? kFlagHostStore : 0u, 0u, zc ? rrte_ctx::kZcProf : 0);
         c->tile_shift = 3;
         c->host_out = false;
         if (r == RRTE_OK) r = hipEventRecord(c->ev1, c->stream) == hipSuccess ? RRTE_OK : RRTE_HIP_ERROR;
@@ -751,9 +394,9 @@ rrte_status rrte_hip_render_async(rrte_ctx* c, const rrte_scene_ir* s, const rrt
     uint32_t rows = p->height;
     rrte_render_params pe = *p;
     BandMap bm{0u, 1u, 0u, 1u, 1u};
-    if (c->emu_nranks > 1) {  // diagnostic: exactly one rank's share of a multi-GPU frame, packed
-        c->nranks = c->emu_nranks;
-        c->rank = c->emu_rank;
+    if (c->env.emu_nranks > 1) {  // diagnostic: exactly one rank's share of a multi-GPU frame, packed
+        c->nranks = c->env.emu_nranks;
+        c->rank = c->env.emu_rank;
         pe.band_rows = p->band_rows ? p->band_rows : 16;
         bm = frame_band_map(c, s, &pe, 0, &rows);
     } else {
@@ -765,67 +408,11 @@ rrte_status rrte_hip_render_async(rrte_ctx* c, const rrte_scene_ir* s, const rrt
     c->nranks = nr;
     c->rank = rk;
     if (r != RRTE_OK) return r;
-    c->hpa_frames += c->host_prof;
+    c->hpa_frames += c->env.host_prof;
     c->pending_primary = (uint64_t)p->width * rows * p->samples_per_pixel;
     c->stats.upload_ms = up;
     c->stats.frames++;
     return RRTE_OK;
-}
-
-rrte_status rrte_hip_tile_order_plan(const uint32_t* costs, uint32_t tiles, uint32_t tiles_x, uint32_t* slots,
-                                     uint32_t cap, uint32_t* n_slots) {
-    if (!costs || !slots || !n_slots || tiles == 0 || tiles_x == 0 || tiles_x > 0xffffu || tiles / tiles_x > 0xffffu)
-        return RRTE_INVALID_ARG;
-    const std::vector<uint32_t> v = lpt_slots(costs, tiles, tiles_x);
-    *n_slots = (uint32_t)v.size();
-    if (v.size() > cap) return RRTE_INVALID_ARG;
-    std::copy(v.begin(), v.end(), slots);
-    return RRTE_OK;
-}
-
-rrte_status rrte_hip_build_id(char* out, size_t out_len) {
-    if (!out || out_len < 33) return RRTE_INVALID_ARG;
-    // the device code's identity: the embedded headers, every hiprtc option (RRTE_JIT_EXTRA_OPTS
-    // included) and the hiprtc version -- the JIT cache key of an empty source
-    snprintf(out, out_len, "%s", jit_cache_name(std::string(), nullptr).c_str());
-    return RRTE_OK;
-}
-
-rrte_status rrte_hip_jit_cache_key(const char* source, const char* headers_override, char* out, size_t out_len) {
-    if (!source || !out || out_len < 33) return RRTE_INVALID_ARG;
-    snprintf(out, out_len, "%s", jit_cache_name(source, headers_override).c_str());
-    return RRTE_OK;
-}
-
-rrte_status rrte_hip_jit_check(const rrte_scene_ir* s, int mode, char* log, size_t log_len) {
-    if (!s || (s->num_prims && !s->prims) || (s->num_sdf_nodes && !s->sdf_nodes)) return RRTE_INVALID_ARG;
-    std::vector<DPrim> prims;
-    std::vector<DMaterial> mats;
-    std::vector<DLight> lights;
-    if ((s->num_mesh_indices && !s->mesh_indices) || (s->num_mesh_vertices && !s->mesh_vertices)) return RRTE_INVALID_ARG;
-    lower_scene(s, prims, mats, lights);
-    MeshData md;
-    build_mesh_bvhs(s, prims.data(), md, nullptr);
-    // RRTE_JIT_CHECK_MULTI=1: the multi-sample / multi-bounce variant (as the renderer picks it for
-    // spp > 1 or max_depth > 1) instead of the straight-line one
-    const char* mv = getenv("RRTE_JIT_CHECK_MULTI");
-    const bool single = !(mv && mv[0] == '1');
-    std::vector<rrte_sdf_node> nodes = decorate_scene_sdf(s, env_guard_setting());
-    JitTopo topo;
-    topology_of(prims, lights, nodes, topo);
-    // RRTE_JIT_TOPO=1: the topology kernel instead of the full one
-    const char* tv = getenv("RRTE_JIT_TOPO");
-    const bool want_topo = tv && tv[0] == '1';
-    std::string src = jit_source(prims.data(), (uint32_t)prims.size(), mats.data(), (uint32_t)mats.size(),
-                                 lights.data(), (uint32_t)lights.size(), nodes.data(), s->num_sdf_nodes, mode,
-                                 cull_policy(s, (uint32_t)mode, env_cull_setting()), single,
-                                 want_topo ? &topo : nullptr);
-    std::string msg;
-    bool ok = jit_compile_only(src, msg);
-    if (log && log_len) {
-        snprintf(log, log_len, "%s", ok ? "" : msg.c_str());
-    }
-    return ok ? RRTE_OK : RRTE_HIP_ERROR;
 }
 
 }  // extern "C"
@@ -850,14 +437,7 @@ rrte_status query_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st) {
     if ((r = upload_scene(c, s, st, &up)) != RRTE_OK) return r;
     // a query of the cached scene is not a render of it (JIT AUTO counts consecutive renders)
     if (c->same_scene_renders == renders + 1) c->same_scene_renders = renders;
-    if (c->sb_cur >= 0) {
-        rrte_ctx::SceneBuf& B = c->sb[c->sb_cur];
-        if (std::find(B.ordered.begin(), B.ordered.end(), st) == B.ordered.end()) {
-            HIPCHK(c, ev_wait(c, st, B.ev_up, "wait scene upload"));
-            B.ordered.push_back(st);
-        }
-        B.ret.use(st);
-    }
+    if (c->sb_cur >= 0) HIPCHK(c, c->sb[c->sb_cur].ver.begin_read(c, st, "wait scene upload"));
     c->launched.use(st);
     return RRTE_OK;
 }
@@ -867,7 +447,7 @@ rrte_status query_launch(rrte_ctx* c, const rrte_scene_ir* s, const void* d_in, 
                          const QueryCam* qc, void* d_hits, hipStream_t st, bool fresh_count = true) {
     const SceneView sv{c->d_prims, c->d_mats, c->d_lights, c->d_nodes, s->num_prims, s->num_lights, s->num_materials,
                        c->mesh_view};
-    const uint32_t need = c->env_generic_all ? (kFeatAll | (c->scene_feat & kFeatInstance)) : c->scene_feat;
+    const uint32_t need = c->env.generic_all ? (kFeatAll | (c->scene_feat & kFeatInstance)) : c->scene_feat;
     static const QueryCam no_cam{};
     trace_rec(c, "launch query", st, nullptr, n, flags);
     if (c->accel_on) {
@@ -900,8 +480,8 @@ rrte_status query_blocking(rrte_ctx* c, const rrte_scene_ir* s, const void* in, 
     rrte_status r = query_scene(c, s, c->stream);
     if (r != RRTE_OK) return r;
     const uint32_t chunk = std::min(n, kQueryChunk);
-    if ((r = ensure(c, c->d_qin, c->cap_qin, (size_t)chunk * in_stride)) != RRTE_OK) return r;
-    if ((r = ensure(c, c->d_qout, c->cap_qout, (size_t)chunk * sizeof(rrte_ray_hit))) != RRTE_OK) return r;
+    if ((r = ensure(c, c->d_qin, (size_t)chunk * in_stride)) != RRTE_OK) return r;
+    if ((r = ensure(c, c->d_qout, (size_t)chunk * sizeof(rrte_ray_hit))) != RRTE_OK) return r;
     for (uint32_t done = 0; done < n; done += chunk) {
         const uint32_t m = std::min(chunk, n - done);
         HIPCHK(c, hipMemcpyAsync(c->d_qin, static_cast<const uint8_t*>(in) + (size_t)done * in_stride,

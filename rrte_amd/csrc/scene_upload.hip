@@ -404,15 +404,15 @@ static rrte_status build_meshes_device(rrte_ctx* c, const rrte_scene_ir* s, Mesh
     *done = false;
     const auto t0 = std::chrono::steady_clock::now();
     const bool planned = c->builder.plan(s);
-    if (c->host_prof)  // (a refused plan has paid for its scan too)
+    if (c->env.host_prof)  // (a refused plan has paid for its scan too)
         c->build_times.host_scan += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     if (!planned) return RRTE_OK;
     rrte_status r;
-    if ((r = ensure(c, c->d_build, c->cap_build, c->builder.scratch_bytes())) != RRTE_OK) return r;
+    if ((r = ensure(c, c->d_build, c->builder.scratch_bytes())) != RRTE_OK) return r;
     uint32_t depth = 0;
     hipError_t err = hipSuccess;
-    const BuildResult br = c->builder.run(s, c->d_build, c->upload_stream, (c->env_debug & 4u) ? c->d_counters + 1 : nullptr,
-                                          built, &depth, &err, c->host_prof ? &c->build_times : nullptr);
+    const BuildResult br = c->builder.run(s, c->d_build, c->upload_stream, (c->env.debug & 4u) ? c->d_counters + 1 : nullptr,
+                                          built, &depth, &err, c->env.host_prof ? &c->build_times : nullptr);
     if (br == BuildResult::HipError) HIPCHK(c, err);
     if (br != BuildResult::Built) {
         built = MeshData{};
@@ -445,7 +445,7 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
     const auto t_up0 = std::chrono::steady_clock::now();
     auto t_sec = t_up0;
     auto lap_up = [&](int i) {  // (RRTE_HOST_PROFILE)
-        if (!c->host_prof) return;
+        if (!c->env.host_prof) return;
         const auto n = std::chrono::steady_clock::now();
         c->hpu[i] += std::chrono::duration<double, std::micro>(n - t_sec).count();
         t_sec = n;
@@ -497,7 +497,7 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
                                                          kAccelStack, atree) == AccelBuild::Built;
     lap_up(1);
     // SDF programs with their exact CSG early-outs (sdf_guard.hpp); the key above stays the caller's IR
-    std::vector<rrte_sdf_node> nodes = decorate_scene_sdf(s, c->env_guard_leaves);
+    std::vector<rrte_sdf_node> nodes = decorate_scene_sdf(s, c->env.guard_leaves);
     lap_up(2);
     JitTopo topo;
     std::string tkey = topology_of(prims, lights, nodes, topo);
@@ -508,10 +508,10 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
     // means more scene changes than versions within the frames in flight; bounded, like every wait
     // that may sit behind a gather)
     rrte_status r;
-    if (c->sb_cur >= 0 && (r = retire(c, c->sb[c->sb_cur].ret)) != RRTE_OK) return r;
+    if (c->sb_cur >= 0 && (r = c->sb[c->sb_cur].ver.retire(c)) != RRTE_OK) return r;
     const int nx = (c->sb_cur + 1) % rrte_ctx::kSceneVersions;
     rrte_ctx::SceneBuf& B = c->sb[nx];
-    if ((r = wait_retired(c, B.ret)) != RRTE_OK) return r;
+    if ((r = B.ver.wait_retired(c)) != RRTE_OK) return r;
     c->same_scene_renders = 0;
     ++c->scene_gen;
     c->sb_cur = -1;  // (until the upload has completed: a failure below leaves no current version)
@@ -553,27 +553,21 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
     }
     total = std::max<size_t>(total, 256u);
     // the staging buffer may still feed this version's previous upload if no launch ever read it
-    if (B.ev_up) HIPCHK(c, hipEventSynchronize(B.ev_up));  // (upload stream: copies only, bounded)
-    if ((r = ensure(c, B.d_buf, B.cap, total)) != RRTE_OK) return r;
-    if (B.cap_h < total) {
-        if (B.h_stage) (void)hipHostFree(B.h_stage);  // (its copies have completed: ev_up above)
-        B.h_stage = nullptr;
-        B.cap_h = 0;
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&B.h_stage), total, hipHostMallocDefault));
-        B.cap_h = total;
-    }
-    if (!B.ev_up) HIPCHK(c, hipEventCreateWithFlags(&B.ev_up, hipEventDisableTiming));
+    if (B.ver.ev_up) HIPCHK(c, hipEventSynchronize(B.ver.ev_up));  // (upload stream: copies only, bounded)
+    if ((r = ensure(c, B.d_buf, total)) != RRTE_OK) return r;
+    HIPCHK(c, B.h_stage.grow(total));  // (its copies have completed: ev_up above)
+    HIPCHK(c, B.ver.ev_up.create());
     for (const Part& pt : parts)
         if (pt.bytes) memcpy(B.h_stage + pt.off, pt.src, pt.bytes);
     lap_up(5);
     hipStream_t us = c->upload_stream;  // (created with the context)
     // fault injection for the check below (RRTE_FAULT_BAD_SLOT=2 with RRTE_DEBUG bit 2): object 0's
     // kind out of range in the device copy only (kernels skip an unknown kind; the host copy stays valid)
-    if (c->env_fault_bad_slot == 2 && (c->env_debug & 4u) && !prims.empty())
+    if (c->env.fault_bad_slot == 2 && (c->env.debug & 4u) && !prims.empty())
         reinterpret_cast<DPrim*>(B.h_stage + parts[kPartPrims].off)->kind = 0xbadu;
     HIPCHK(c, hipMemcpyAsync(B.d_buf, B.h_stage, total, hipMemcpyHostToDevice, us));
     lap_up(6);
-    if ((c->env_debug & 4u) && !prims.empty()) {
+    if ((c->env.debug & 4u) && !prims.empty()) {
         hipLaunchKernelGGL(scene_records_check, dim3(((uint32_t)prims.size() + 63u) / 64u), dim3(64), 0, us,
                            reinterpret_cast<const DPrim*>(B.d_buf + parts[kPartPrims].off), (uint32_t)prims.size(),
                            reinterpret_cast<const rrte_sdf_node*>(B.d_buf + parts[kPartNodes].off), (uint32_t)nodes.size(),
@@ -592,13 +586,12 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
         rd.n_verts = s->num_mesh_vertices;
         rd.n_slots = (uint32_t)(md.tris.size() / 3);
         rd.n_recs = (uint32_t)(md.nodes.size() / 4);
-        rd.check = (c->env_debug & 4u) ? c->d_counters + 1 : nullptr;
+        rd.check = (c->env.debug & 4u) ? c->d_counters + 1 : nullptr;
         HIPCHK(c, launch_refit(rs, rd, us));
         ++c->device_refits;
     }
-    HIPCHK(c, hipEventRecord(B.ev_up, us));
+    HIPCHK(c, B.ver.published(us));
     lap_up(7);
-    B.ordered.clear();
     // host time to lower the scene and enqueue its upload (the copy itself is asynchronous)
     *upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_up0).count();
     uint8_t* d = B.d_buf;
@@ -646,7 +639,7 @@ rrte_status upload_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st, do
         k += kparts.lens[i];
     }
     lap_up(8);
-    c->hpu_n += c->host_prof;
+    c->hpu_n += c->env.host_prof;
     return RRTE_OK;
 }
 
@@ -707,7 +700,7 @@ rrte_status rrte_hip_mesh_nodes(rrte_ctx* c, void* out, size_t bytes, uint32_t* 
     *records = (uint32_t)(c->mesh_cache.nodes.size() / 4);
     const size_t n = std::min(bytes, all);
     if (!n) return RRTE_OK;
-    if (B.ev_up) HIPCHK(c, hipEventSynchronize(B.ev_up));
+    if (B.ver.ev_up) HIPCHK(c, hipEventSynchronize(B.ver.ev_up));
     HIPCHK(c, hipMemcpy(out, c->mesh_view.nodes, n, hipMemcpyDeviceToHost));
     return RRTE_OK;
 }
