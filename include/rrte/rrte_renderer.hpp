@@ -24,6 +24,7 @@
 #include "../rrte_hip.h"
 #include "../rrte_hip_accel.h"
 #include "../rrte_hip_build.h"
+#include "../rrte_hip_aov.h"
 #include "../rrte_hip_query.h"
 #include "../rrte_hip_refit.h"
 
@@ -391,6 +392,21 @@ private:
     rrte_scene_ir ir_{};
 };
 
+// The planes Raytracer::render_aov returns (include/rrte_hip_aov.h): row-major over the width x height
+// rectangle, row 0 = top; a plane that was not requested is empty.  normal, position and albedo hold
+// four floats per pixel.
+struct AovPlanes {
+    uint32_t width = 0, height = 0;
+    std::vector<float> depth;
+    std::vector<int32_t> prim, material;
+    std::vector<uint32_t> tri;
+    std::vector<float> normal, position, albedo;
+};
+// A rectangle of the frame in pixels; all zero = the whole frame.
+struct AovRect {
+    uint32_t x0 = 0, y0 = 0, width = 0, height = 0;
+};
+
 class Raytracer {
 public:
     explicit Raytracer(RaytracerConfig config = {}, int device = 0);
@@ -441,6 +457,11 @@ public:
     // the frame's own pixel-centre primary ray, t_min = config.t_min.
     std::vector<rrte_ray_hit> pick(const Objects& objects, const Camera& camera,
                                    const std::vector<std::pair<uint32_t, uint32_t>>& pixels, const Lights& lights = {});
+    // Frame AOVs (include/rrte_hip_aov.h): what the pixel-centre primary ray of every pixel of `rect`
+    // (of the configured width x height frame seen by `camera`) hit, one array per plane of the mask
+    // `planes` (RRTE_AOV_*).  Each value is the field of the record pick() returns for that pixel.
+    AovPlanes render_aov(const Objects& objects, const Camera& camera, uint32_t planes = RRTE_AOV_ALL,
+                         const AovRect& rect = {}, const Lights& lights = {});
     rrte_stats stats() const;
     // the C ABI call on an already lowered scene (diagnostics, tests/cpp/cpp_mirror_tool.cpp)
     void render_raw(const rrte_scene_ir& ir, const rrte_render_params& p, uint8_t* out) {

@@ -184,6 +184,36 @@ QUERY_EXPORTS = {
                                 C.POINTER(RayHit)]),
 }
 
+# ------------------------------------------------ frame AOVs (include/rrte_hip_aov.h)
+AOV_DEPTH, AOV_PRIM, AOV_MATERIAL, AOV_TRI, AOV_NORMAL, AOV_POSITION, AOV_ALBEDO = (1 << k for k in range(7))
+AOV_ALL = 0x7F
+# plane name (the field of AovBuffers) -> (bit, numpy dtype, floats per pixel: 4 for a float[4] plane, else 0)
+AOV_PLANES = {"depth": (AOV_DEPTH, "<f4", 0), "prim": (AOV_PRIM, "<i4", 0), "material": (AOV_MATERIAL, "<i4", 0),
+              "tri": (AOV_TRI, "<u4", 0), "normal": (AOV_NORMAL, "<f4", 4), "position": (AOV_POSITION, "<f4", 4),
+              "albedo": (AOV_ALBEDO, "<f4", 4)}
+
+
+class AovDesc(C.Structure):
+    _fields_ = [("planes", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("_pad", C.c_uint32 * 3)]
+
+
+class AovBuffers(C.Structure):
+    _fields_ = [("depth", C.POINTER(C.c_float)), ("prim", C.POINTER(C.c_int32)), ("material", C.POINTER(C.c_int32)),
+                ("tri", C.POINTER(C.c_uint32)), ("normal", C.POINTER(C.c_float)), ("position", C.POINTER(C.c_float)),
+                ("albedo", C.POINTER(C.c_float)), ("_reserved", C.c_void_p)]
+
+
+assert C.sizeof(AovDesc) == 32 and C.sizeof(AovBuffers) == 64
+
+# Every entry point include/rrte_hip_aov.h declares.
+AOV_EXPORTS = {
+    "rrte_hip_render_aov": (C.c_int, [_P, C.POINTER(SceneIR), C.POINTER(RenderParams), C.POINTER(AovDesc),
+                                      C.POINTER(AovBuffers)]),
+    "rrte_hip_render_aov_async": (C.c_int, [_P, C.POINTER(SceneIR), C.POINTER(RenderParams), C.POINTER(AovDesc),
+                                            C.POINTER(AovBuffers), _P]),
+}
+
 # ------------------------------------------------ mesh sharing diagnostics (include/rrte_hip_mesh.h)
 class MeshInfo(C.Structure):
     _fields_ = [("bvh_builds", C.c_uint64), ("ranges", C.c_uint32), ("tri_slots", C.c_uint32),
@@ -299,7 +329,7 @@ def load() -> C.CDLL:
         pass
     lib = C.CDLL(str(LIB_PATH), mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**EXPORTS, **QUERY_EXPORTS, **MESH_EXPORTS, **REFIT_EXPORTS, **BUILD_EXPORTS,
-                               **ACCEL_EXPORTS, **JIT_EXPORTS, **CLIP_EXPORTS}.items():
+                               **ACCEL_EXPORTS, **JIT_EXPORTS, **CLIP_EXPORTS, **AOV_EXPORTS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -743,6 +743,32 @@ std::vector<rrte_ray_hit> Raytracer::pick(const Objects& objects, const Camera& 
     check(rrte_hip_pick(ctx_, &sc.ir(), &p, xy.data(), (uint32_t)pixels.size(), hits.data()));
     return hits;
 }
+AovPlanes Raytracer::render_aov(const Objects& objects, const Camera& camera, uint32_t planes, const AovRect& rect,
+                                const Lights& lights) {
+    const LoweredScene sc(objects, lights, camera);
+    const rrte_render_params p = config_.lower();
+    const bool whole = !(rect.x0 | rect.y0 | rect.width | rect.height);
+    AovPlanes out;
+    out.width = whole ? p.width : rect.width;
+    out.height = whole ? p.height : rect.height;
+    const size_t n = (size_t)out.width * out.height;
+    rrte_aov_desc d{};
+    d.planes = planes;
+    d.x0 = rect.x0;
+    d.y0 = rect.y0;
+    d.width = rect.width;
+    d.height = rect.height;
+    rrte_aov_buffers b{};
+    if (planes & RRTE_AOV_DEPTH) out.depth.resize(n), b.depth = out.depth.data();
+    if (planes & RRTE_AOV_PRIM) out.prim.resize(n), b.prim = out.prim.data();
+    if (planes & RRTE_AOV_MATERIAL) out.material.resize(n), b.material = out.material.data();
+    if (planes & RRTE_AOV_TRI) out.tri.resize(n), b.tri = out.tri.data();
+    if (planes & RRTE_AOV_NORMAL) out.normal.resize(4 * n), b.normal = out.normal.data();
+    if (planes & RRTE_AOV_POSITION) out.position.resize(4 * n), b.position = out.position.data();
+    if (planes & RRTE_AOV_ALBEDO) out.albedo.resize(4 * n), b.albedo = out.albedo.data();
+    check(rrte_hip_render_aov(ctx_, &sc.ir(), &p, &d, &b));
+    return out;
+}
 rrte_stats Raytracer::stats() const {
     rrte_stats s;
     check(rrte_hip_stats(ctx_, &s));

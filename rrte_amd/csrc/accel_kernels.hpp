@@ -235,9 +235,20 @@ __global__ __launch_bounds__(kBlockThreads, 4) void ray_kernel_accel(KParams kp,
     ray_kernel_body<MODE, SceneViewAccel, false, false>(kp, s, Cull{nullptr, 0u}, out_rgba8, out_f32, counters);
 }
 
-// The accelerated query kernel: ray_query_kernel (ray_query.hpp) with its two object loops over the
-// candidates.  Everything else -- ray set-up, idle lanes, the attribute walk, the stores -- is that
-// kernel's, statement for statement.
+// `visit` of closest_hit_search (ray_query.hpp) for the accelerated scene: the candidates `groups` of
+// a walk, in list order.
+__device__ __forceinline__ auto visit_candidates(const AccelView& av, uint64_t groups) {
+    return [&av, groups](auto&& f) {
+        accel_for_each(av, groups, [&](uint32_t k) {
+            f(k);
+            return true;
+        });
+    };
+}
+
+// The accelerated query kernel: ray_query_kernel (ray_query.hpp) with its object loops over the
+// candidates: the any-hit loop here, the closest-hit search the one body of closest_hit_search.  Ray
+// set-up, idle lanes and the stores are that kernel's, statement for statement.
 template <bool ANY, bool PICK>
 __global__ __launch_bounds__(kBlockThreads) void ray_query_accel_kernel(SceneView scv, AccelView av,
                                                                         const void* __restrict__ in, uint32_t n, QueryCam qc,
@@ -282,30 +293,10 @@ __global__ __launch_bounds__(kBlockThreads) void ray_query_accel_kernel(SceneVie
             return !__all(idx >= 0 || !live);
         });
     } else {
-        float best_t = kInf;
-        uint32_t best_sub = 0u;
-        accel_for_each(sc.acc, groups, [&](uint32_t k) {
-            Hit hk;
-            hk.sub = 0u;
-            const bool sdf = load_uniform(&sc.prims[k].kind) == RRTE_PRIM_SDF;
-            const float tm = (sdf && idx >= 0) ? (t_max < best_t ? t_max : best_t) : t_max;
-            if (intersect_at<false>(sc, k, r, t_min, tm, hk) && live) {
-                if (idx < 0 || hk.t < best_t) {
-                    best_t = hk.t;
-                    best_sub = hk.sub;
-                    idx = (int)k;
-                }
-            }
-            return true;
-        });
-        bool pending = idx >= 0;
-        while (pending) {
-            const uint32_t w = __builtin_amdgcn_readfirstlane((uint32_t)idx);
-            if ((uint32_t)idx == w) {
-                query_attributes(sc, w, r, t_min, t_max, best_t, best_sub, h, tri);
-                pending = false;
-            }
-        }
+        const ClosestHit c = closest_hit_search(sc, r, t_min, t_max, live, visit_candidates(sc.acc, groups));
+        idx = c.idx;
+        h = c.h;
+        tri = c.tri;
     }
     if (live) {
         const int material = idx >= 0 ? sc.prims[idx].material : -1;

@@ -221,6 +221,8 @@ struct rrte_ctx {
     rrte::DeviceBuf<float4> d_f32;
     // staging of the blocking ray queries (rrte_hip_raycast / rrte_hip_pick): rays or pixel pairs in, hits out
     rrte::DeviceBuf<uint8_t> d_qin, d_qout;
+    // staging of the blocking frame AOVs (rrte_hip_render_aov): one chunk of every requested plane
+    rrte::DeviceBuf<uint8_t> d_aov;
     rrte::DeviceBuf<unsigned long long> d_counters;  // shadow rays, kCounterShards x kCounterStride (accumulating)
     rrte::PinnedBuf<unsigned long long> h_counters;  // pinned copy
     unsigned long long shadow_base = 0;         // value at the start of the last frame
@@ -565,6 +567,12 @@ hipError_t load_ray_kernels();
 rrte_status resolve_counters(rrte_ctx* c);
 rrte_status finish_frame(rrte_ctx* c, bool deferred = false);
 void dump_if_asked(const rrte_ctx* c, const rrte_scene_ir* s, const rrte_render_params* p);
+// Rays (pixels) per launch of the blocking queries and AOVs: bounds the context's staging buffers
+// however large the call is.
+constexpr uint32_t kQueryChunk = 1u << 22;
+rrte_status accel_launch_view(rrte_ctx* c, hipStream_t st, AccelView& av, bool fresh = true);
+rrte_status accel_launch_done(rrte_ctx* c, hipStream_t st);
+rrte_status query_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st);
 
 // gather.hip
 rrte_status render_batch(rrte_ctx* c, bool at_flush);

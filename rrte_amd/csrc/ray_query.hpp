@@ -76,6 +76,68 @@ __device__ __forceinline__ void query_attributes(const S& sc, uint32_t i, const 
     if constexpr ((F & kFeatAnalytic) != 0u) intersect_at<true>(sc, i, r, t_min, t_max, out);
 }
 
+// What the closest-hit search returns: the winning object (-1: none), its hit record (the miss
+// record t = +inf, everything else zero, when there is none) and, for a mesh or mesh instance, the
+// triangle's index within its range.
+struct ClosestHit {
+    int idx;
+    Hit h;
+    uint32_t tri;
+};
+
+// The closest-hit search of a query, one body for every kernel that runs it (the query kernels below,
+// the accelerated ones of accel_kernels.hpp, the view kernels of aov_kernels.hpp).  `visit(f)` calls
+// f(k) for the objects to test, in list order: every object, or the accelerator's candidates.
+//
+// Idle lanes (`live` false) stay in the wave -- the search holds wave-wide operations -- with a benign
+// ray over the empty interval [+inf, -inf] and never win.  raytracer.rs:103-113: list order, strict
+// '<'; an SDF object marches only up to the closest hit so far (closest_t of the frame kernel, with the
+// ray's own t_max).  The wave then walks its distinct winners (hit_attributes of the frame kernel).
+template <class S, class Visit>
+__device__ __forceinline__ ClosestHit closest_hit_search(const S& sc, const Ray& r, float t_min, float t_max, bool live,
+                                                         Visit&& visit) {
+    ClosestHit c;
+    c.idx = -1;
+    c.h.t = kInf;
+    c.h.p = V(0.0f, 0.0f, 0.0f);
+    c.h.n = V(0.0f, 0.0f, 0.0f);
+    c.h.front = false;
+    c.h.sub = 0u;
+    c.tri = 0u;
+    float best_t = kInf;
+    uint32_t best_sub = 0u;
+    visit([&](uint32_t k) {
+        Hit hk;
+        hk.sub = 0u;
+        const bool sdf = load_uniform(&sc.prims[k].kind) == RRTE_PRIM_SDF;
+        const float tm = (sdf && c.idx >= 0) ? (t_max < best_t ? t_max : best_t) : t_max;
+        if (intersect_at<false>(sc, k, r, t_min, tm, hk) && live) {
+            if (c.idx < 0 || hk.t < best_t) {
+                best_t = hk.t;
+                best_sub = hk.sub;
+                c.idx = (int)k;
+            }
+        }
+    });
+    bool pending = c.idx >= 0;
+    while (pending) {
+        const uint32_t w = __builtin_amdgcn_readfirstlane((uint32_t)c.idx);
+        if ((uint32_t)c.idx == w) {
+            query_attributes(sc, w, r, t_min, t_max, best_t, best_sub, c.h, c.tri);
+            pending = false;
+        }
+    }
+    return c;
+}
+
+// `visit` of closest_hit_search for the plain scene: every object.
+template <class S>
+__device__ __forceinline__ auto visit_all(const S& sc) {
+    return [&sc](auto&& f) {
+        for (uint32_t k = 0; k < sc.num_prims; ++k) f(k);
+    };
+}
+
 // ANY: RRTE_QUERY_ANY, else RRTE_QUERY_CLOSEST.  PICK: `in` holds n (x, y) pixel pairs and the rays
 // are qc's pixel-centre camera rays; else `in` holds n rrte_ray records.  F: the scene features
 // compiled in (the host picks the variant as launch_generic does).
@@ -124,32 +186,10 @@ __global__ __launch_bounds__(kBlockThreads) void ray_query_kernel(SceneView scv,
             if (__all(idx >= 0 || !live)) break;
         }
     } else {
-        // raytracer.rs:103-113: list order, strict '<'; an SDF object marches only up to the closest
-        // hit so far (closest_t of the frame kernel, with the ray's own t_max)
-        float best_t = kInf;
-        uint32_t best_sub = 0u;
-        for (uint32_t k = 0; k < sc.num_prims; ++k) {
-            Hit hk;
-            hk.sub = 0u;
-            const bool sdf = load_uniform(&sc.prims[k].kind) == RRTE_PRIM_SDF;
-            const float tm = (sdf && idx >= 0) ? (t_max < best_t ? t_max : best_t) : t_max;
-            if (intersect_at<false>(sc, k, r, t_min, tm, hk) && live) {
-                if (idx < 0 || hk.t < best_t) {
-                    best_t = hk.t;
-                    best_sub = hk.sub;
-                    idx = (int)k;
-                }
-            }
-        }
-        // the wave walks its distinct winners (hit_attributes of the frame kernel)
-        bool pending = idx >= 0;
-        while (pending) {
-            const uint32_t w = __builtin_amdgcn_readfirstlane((uint32_t)idx);
-            if ((uint32_t)idx == w) {
-                query_attributes(sc, w, r, t_min, t_max, best_t, best_sub, h, tri);
-                pending = false;
-            }
-        }
+        const ClosestHit c = closest_hit_search(sc, r, t_min, t_max, live, visit_all(sc));
+        idx = c.idx;
+        h = c.h;
+        tri = c.tri;
     }
     if (live) {
         const int material = idx >= 0 ? sc.prims[idx].material : -1;

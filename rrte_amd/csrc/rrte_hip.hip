@@ -24,6 +24,7 @@
 //   tile_order.hip    the tile order of a launch (TileProfile: lpt_slots, fixed_slots, reserve_hot_lists,
 //                     upload_hot_list, plan_tile_order, finish_tile_order: issue_launch is their only
 //                     caller), rrte_hip_tile_order_plan
+//   aov.hip           rrte_hip_render_aov / render_aov_async (include/rrte_hip_aov.h; kernels: aov_kernels.hpp)
 //   rrte_hip.hip      launch_generic (the generic kernel variant), plain_launch, issue_launch, launch,
 //                     resolve_counters, finish_frame,
 //                     render_chunked, render_common, dump_if_asked, rrte_hip_render*, the ray queries
@@ -82,7 +83,7 @@ static bool plain_launch(const rrte_ctx* c, const JitKernel* jk, const LaunchPla
 // counts into two spare words of counter shard 0 (words 2 and 3 of its 128-B line: word 0 is the
 // shadow-ray count, word 1 the check word), cleared on `st` ahead of it; `fresh` false continues the
 // counts of the launch before (the later chunks of one blocking query).
-static rrte_status accel_launch_view(rrte_ctx* c, hipStream_t st, AccelView& av, bool fresh = true) {
+rrte_status accel_launch_view(rrte_ctx* c, hipStream_t st, AccelView& av, bool fresh) {
     av = c->accel;
     if (!(c->accel_flags & RRTE_ACCEL_COUNT)) return RRTE_OK;
     av.count = c->d_counters + 2;
@@ -93,7 +94,7 @@ static rrte_status accel_launch_view(rrte_ctx* c, hipStream_t st, AccelView& av,
 
 // Behind an accelerated launch on `st`: under RRTE_ACCEL_COUNT the event rrte_hip_accel_info waits for
 // (an event, not the stream: the caller may destroy its stream once its work is done).
-static rrte_status accel_launch_done(rrte_ctx* c, hipStream_t st) {
+rrte_status accel_launch_done(rrte_ctx* c, hipStream_t st) {
     if (!(c->accel_flags & RRTE_ACCEL_COUNT)) return RRTE_OK;
     HIPCHK(c, hipEventRecord(c->ev_accel, st));
     c->accel_counted = true;
@@ -420,11 +421,8 @@ rrte_status rrte_hip_render_async(rrte_ctx* c, const rrte_scene_ir* s, const rrt
 // ------------------------------------------------- ray queries (include/rrte_hip_query.h)
 // Closest hit, any hit and pixel picking over the cached scene (kernel: ray_query.hpp).  Local
 // calls: no collective, no gather-batch close, rrte_stats untouched.
-namespace {
-
-// Rays per launch of the blocking forms: bounds the context's staging buffers (128 MiB of rays,
-// 192 MiB of hits) however large the call is.
-constexpr uint32_t kQueryChunk = 1u << 22;
+// (kQueryChunk rays per launch of the blocking forms: 128 MiB of rays, 192 MiB of hits)
+namespace rrte {
 
 // The scene of a query, cached and readable on `st`: validated, uploaded through the context's scene
 // cache if it differs from the cached one, `st` ordered after the version's upload and registered with
@@ -441,6 +439,10 @@ rrte_status query_scene(rrte_ctx* c, const rrte_scene_ir* s, hipStream_t st) {
     c->launched.use(st);
     return RRTE_OK;
 }
+
+}  // namespace rrte
+
+namespace {
 
 // Enqueue one query launch of n rays (or n pixel pairs with `qc`) on `st`.
 rrte_status query_launch(rrte_ctx* c, const rrte_scene_ir* s, const void* d_in, uint32_t n, uint32_t flags,

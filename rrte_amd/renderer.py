@@ -1145,6 +1145,62 @@ class Raytracer:
                                         len(xy), hits.ctypes.data_as(C.POINTER(abi.RayHit))))
         return hits
 
+    # ------------------------------------------------------- frame AOVs (include/rrte_hip_aov.h)
+    @staticmethod
+    def aov_mask(planes) -> int:
+        """A plane mask from an int (abi.AOV_*) or from plane names ("depth", "prim", "material",
+        "tri", "normal", "position", "albedo")."""
+        if isinstance(planes, int):
+            return planes
+        mask = 0
+        for name in ([planes] if isinstance(planes, str) else planes):
+            mask |= abi.AOV_PLANES[name][0]
+        return mask
+
+    def _aov_desc(self, planes, rect):
+        x0, y0, w, h = rect if rect is not None else (0, 0, 0, 0)
+        return abi.AovDesc(planes=self.aov_mask(planes), x0=x0, y0=y0, width=w, height=h)
+
+    def render_aov(self, objects, camera: Camera, planes=abi.AOV_ALL, rect=None, lights=()) -> dict:
+        """What the pixel-centre primary ray of every pixel hit, as one array per requested plane
+        (rrte_hip_render_aov): `planes` is a mask of abi.AOV_* or a list of plane names, `rect` =
+        (x0, y0, width, height) in pixels of the configured frame (None, or all zero as in the
+        header: the whole frame).  Returns
+        {name: array}: shape (h, w) for depth (f32), prim, material (i32) and tri (u32), (h, w, 4)
+        f32 for normal (w = front face), position (w = 1 on a hit) and albedo.  Each value is the
+        field of the record pick() returns for that pixel (prim = -1, depth = +inf: a miss).
+        `lights`: as for raycast()."""
+        desc = self._aov_desc(planes, rect)
+        # the arrays are sized as the library reads the desc: an all-zero rectangle is the whole frame
+        whole = not (desc.x0 | desc.y0 | desc.width | desc.height)
+        w, h = (self.config.width, self.config.height) if whole else (desc.width, desc.height)
+        out, bufs = {}, abi.AovBuffers()
+        for name, (bit, dtype, comps) in abi.AOV_PLANES.items():
+            if desc.planes & bit:
+                out[name] = np.zeros((h, w, comps) if comps else (h, w), dtype=dtype)
+                setattr(bufs, name, out[name].ctypes.data_as(type(getattr(bufs, name))))
+        scene = LoweredScene(objects, lights, camera)
+        prm = self.config.lower()
+        ctx = self.ctx
+        ctx.check(ctx.lib.rrte_hip_render_aov(ctx.h, scene.ref(), C.byref(prm), C.byref(desc), C.byref(bufs)))
+        return out
+
+    def render_aov_async(self, objects, camera: Camera, planes, d_planes: dict, rect=None, stream: int | None = None,
+                         lights=()):
+        """rrte_hip_render_aov_async: the planes into device memory, `d_planes` = {name: device
+        address} (float[4] planes 16-byte aligned), enqueued on `stream` (a hipStream_t as an integer;
+        None = the context's stream).  Returns at once; the stream must stay valid until the context
+        is next synchronised."""
+        desc = self._aov_desc(planes, rect)
+        bufs = abi.AovBuffers()
+        for name, addr in d_planes.items():
+            setattr(bufs, name, C.cast(C.c_void_p(addr), type(getattr(bufs, name))))
+        scene = LoweredScene(objects, lights, camera)
+        prm = self.config.lower()
+        ctx = self.ctx
+        ctx.check(ctx.lib.rrte_hip_render_aov_async(ctx.h, scene.ref(), C.byref(prm), C.byref(desc), C.byref(bufs),
+                                                    stream))
+
     @staticmethod
     def hit_objects(objects, hits) -> list:
         """The Python object behind each hit record: None for a miss, the object, or for a Mesh the

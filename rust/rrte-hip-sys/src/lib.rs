@@ -172,3 +172,5 @@ pub mod refit;
 pub mod build;
 // the scene accelerator, a top-level BVH over the objects (include/rrte_hip_accel.h): likewise
 pub mod accel;
+// frame AOVs, per-pixel depth / ids / normal / position / albedo of a view (include/rrte_hip_aov.h): likewise
+pub mod aov;
